@@ -19,6 +19,14 @@ multi-GPU: states are independent (moeva2.py:194-205).  Every step runs
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W] [--shard]
                     [--crossover two_point|sbx] [--mlp-dtype fp32|bf16]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (the headline
+figure, ms_per_step).  --dump-outputs DIR also writes the last timed step's outputs (the
+final populations: DIR/genes.npy, DIR/F.npy, and DIR/state_index.npy naming the states
+kept); the inputs and seeds are fixed, so two builds compare output for output.  --full adds
+everything else the line can hold: the per-kernel HIP-event pass (kernels, roofline), the
+Moeva2.generate() end-to-end line, the CPU baseline and the other BASELINE configs.
 """
 import argparse
 import json
@@ -249,12 +257,35 @@ def load_traffic(workload):
     return {}
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: cap of the arrays written (whole states, fp64)
+
+
+def dump_outputs(path, genes, F):
+    """Write what the last timed step returned to its caller -- the final populations'
+    genes (states, P, V) and objectives (states, P, 3), fp64 -- as path/genes.npy and
+    path/F.npy.  Above DUMP_BYTES a fixed, seeded sample of whole states is written
+    instead, its state numbers in path/state_index.npy (float64 like the rest)."""
+    n = genes.shape[0]
+    per_state = 8 * genes.shape[1] * (genes.shape[2] + F.shape[2])
+    keep = max(1, min(n, DUMP_BYTES // per_state))
+    idx = np.arange(n)
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    sel = idx.tolist()
+    np.save(os.path.join(path, "genes.npy"), genes[sel].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "F.npy"), F[sel].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "state_index.npy"), idx.astype(np.float64))
+    log(f"dumped {keep} of {n} states' final populations to {path}")
+
+
 def run_workload(name, w, args, device, world, rank, steps, warmup, bf16, crossover,
-                 profile_gens=None, warm_gens=None):
+                 profile_gens=None, warm_gens=None, profile=True, dump_dir=None):
     """Bind the workload's states, time `steps` whole attacks (after `warmup` untimed ones of
-    warm_gens generations, default the full budget), then the per-kernel HIP-event pass (one
-    state group, profile_gens generations, default the full budget).  Returns the result
-    dict (rank 0; None on the other ranks)."""
+    warm_gens generations, default the full budget), write the last step's outputs to
+    dump_dir if given, then (profile) the per-kernel HIP-event pass (one state group,
+    profile_gens generations, default the full budget).  Returns the result dict (rank 0;
+    None on the other ranks)."""
     import torch
     import torch.distributed as dist
 
@@ -336,18 +367,10 @@ def run_workload(name, w, args, device, world, rank, steps, warmup, bf16, crosso
     value = total_evals / elapsed
     ms_per_step = 1000.0 * elapsed / steps
 
-    # ---- roofline of the dominant kernel, measured live with HIP events: the engine hands a
-    # start / stop pair to every profiled launch (hipExtLaunchKernelGGL stamps the kernel's own
-    # start and end, so the averages agree with rocprofv3's; events recorded around the launch
-    # included ~8 us of dispatch gap per k_genc launch).  One state group, so each launch
-    # covers all states of the rank like the rocprofv3 pass of the same command.
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, out[0], out[1])
     if rank != 0:  # only rank 0 reports (it always owns states); the others are done
         return None
-    eng.set_profiling(True)
-    eng.attack_run(profile_gens or G, P, O, seed, ref, 0.05, hmode)
-    torch.cuda.synchronize()
-    kt = eng.kernel_times()
-    eng.set_profiling(False)
     rows = B * O
     Dm = int(eng.prog.mut_feats.shape[0])
     Dm4 = (Dm + 15) // 16 * 16
@@ -363,6 +386,53 @@ def run_workload(name, w, args, device, world, rank, steps, warmup, bf16, crosso
     n_fixed = int((~eng.stored_genes()).sum())
     dims_exec = [Dm - n_fixed] + dims_full[1:]
     exec_flops = 2 * sum(a * b for a, b in zip(dims_exec[:-1], dims_exec[1:]))
+    if args.shard:
+        par = (f"generate_sharded: {B_all} states split over {world} rank(s) ({B} on rank "
+               f"{rank}); one all_gather of the final populations")
+    else:
+        par = (f"generate_sharded: the {B_all} states tiled x{world} = {states_total}, "
+               f"{B} per rank; one all_gather of the final populations")
+    result = {
+        "metric": "candidate fitness evals/sec (whole node) + attack wall-clock per 1k states",
+        "value": value,
+        "unit": "evals/s",
+        "n_gpus": world,
+        "steps": steps,
+        "warmup": warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong" if args.shard else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": data_note(w, B_all),
+        "config": {"workload": name, "states": states_total, "states_per_gpu": B,
+                   "pop_size": P, "n_offsprings": O, "n_gen": G, "norm": w["norm"],
+                   "history": w["history"], "evals_per_state": evals_per_state,
+                   "classifier_dtype": ("bf16 perf mode (bf16 MFMA, fp32 accumulate; not a "
+                                        "parity result)" if bf16 else "f32 (MFMA)"),
+                   "crossover": crossover,
+                   "genes_stored": int(V) - n_fixed,
+                   "schedule": "per-phase kernel chain",
+                   "parallelism": par},
+        "attack_wall_clock_per_1k_states_s": elapsed / steps / states_total * 1000.0,
+        "load_s": load_s,
+        "algorithmic_per_eval": {"bytes": eval_bytes, "flops": eval_flops,
+                                 "executed_flops": exec_flops},
+    }
+    if not profile:  # the plain run: the headline figure alone
+        del eng
+        return result
+
+    # ---- roofline of the dominant kernel, measured live with HIP events: the engine hands a
+    # start / stop pair to every profiled launch (hipExtLaunchKernelGGL stamps the kernel's own
+    # start and end, so the averages agree with rocprofv3's; events recorded around the launch
+    # included ~8 us of dispatch gap per k_genc launch).  One state group, so each launch
+    # covers all states of the rank like the rocprofv3 pass of the same command.
+    eng.set_profiling(True)
+    eng.attack_run(profile_gens or G, P, O, seed, ref, 0.05, hmode)
+    torch.cuda.synchronize()
+    kt = eng.kernel_times()
+    eng.set_profiling(False)
     # per-kernel algorithmic bytes per offspring row:
     #   k_gen : parent genes read + child genes written (2*V*8) + fp32 ML row (Dm4*4) + f2 (8)
     #   k_cons: child genes read (V*8) + f3 (8)
@@ -446,43 +516,9 @@ def run_workload(name, w, args, device, world, rank, steps, warmup, bf16, crosso
     per_gen["dominant"] = max((k for k in kernels if k != "k_survive"),
                               key=lambda k: kernels[k]["avg_launch_ms"])
     dom = per_gen["dominant"]
-    if args.shard:
-        par = (f"generate_sharded: {B_all} states split over {world} rank(s) ({B} on rank "
-               f"{rank}); one all_gather of the final populations")
-    else:
-        par = (f"generate_sharded: the {B_all} states tiled x{world} = {states_total}, "
-               f"{B} per rank; one all_gather of the final populations")
-    result = {
-        "metric": "candidate fitness evals/sec (whole node) + attack wall-clock per 1k states",
-        "value": value,
-        "unit": "evals/s",
-        "n_gpus": world,
-        "steps": steps,
-        "warmup": warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong" if args.shard else "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": data_note(w, B_all),
-        "config": {"workload": name, "states": states_total, "states_per_gpu": B,
-                   "pop_size": P, "n_offsprings": O, "n_gen": G, "norm": w["norm"],
-                   "history": w["history"], "evals_per_state": evals_per_state,
-                   "classifier_dtype": ("bf16 perf mode (bf16 MFMA, fp32 accumulate; not a "
-                                        "parity result)" if bf16 else "f32 (MFMA)"),
-                   "crossover": crossover,
-                   "genes_stored": int(V) - n_fixed,
-                   "schedule": "per-phase kernel chain",
-                   "parallelism": par},
-        "attack_wall_clock_per_1k_states_s": elapsed / steps / states_total * 1000.0,
-        "load_s": load_s,
-        "roofline": kernels[dom],
-        "kernels": kernels,
-        "kernels_avg_ms_per_generation": per_gen,
-        "kernel_times_generations": ng,
-        "algorithmic_per_eval": {"bytes": eval_bytes, "flops": eval_flops,
-                                 "executed_flops": exec_flops},
-    }
+    result.update({"roofline": kernels[dom], "kernels": kernels,
+                   "kernels_avg_ms_per_generation": per_gen,
+                   "kernel_times_generations": ng})
     del eng
     return result
 
@@ -565,6 +601,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="rq1.botnet.static", choices=sorted(WORKLOADS))
     ap.add_argument("--n-gen", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (final populations: genes, F; "
+                         "fp64, a fixed seeded sample of the states above 48 MiB) as DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-kernel "
+                         "event pass (kernels, roofline), Moeva2.generate() end to end, the CPU "
+                         "baseline and the other BASELINE configs (each has its --no-* switch)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-generate", action="store_true",
                     help="skip the Moeva2.generate() end-to-end line (N = 1)")
@@ -607,8 +650,11 @@ def main():
         w["n_gen"] = args.n_gen
     bf16 = args.mlp_dtype == "bf16"
     result = run_workload(args.workload, w, args, device, world, rank, args.steps, args.warmup,
-                          bf16, args.crossover)
-    if rank == 0:
+                          bf16, args.crossover, profile=args.full,
+                          dump_dir=args.dump_outputs)
+    if rank == 0 and not args.full:
+        print(json.dumps(result), flush=True)
+    elif rank == 0:
         if world == 1 and not args.no_generate and not w["model"].startswith("synthetic:"):
             torch.cuda.empty_cache()
             g = time_generate(w, device)

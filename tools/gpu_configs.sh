@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/configs; mkdir -p $O
 run() {  # name, timeout, args...
   local n=$1 t=$2; shift 2
-  timeout -k 10 $t python -u bench.py "$@" > $O/$n.json 2> $O/$n.log
+  timeout -k 10 $t python -u bench.py --full "$@" > $O/$n.json 2> $O/$n.log
   local rc=$?; echo "$n rc=$rc $(python3 tools/show_bench.py $O/$n.json 2>/dev/null | head -1)"
   case $rc in 0) ;; *) exit $rc;; esac
 }

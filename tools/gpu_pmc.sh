@@ -10,7 +10,7 @@ while read -r group; do
   [ -z "$group" ] && continue
   i=$((i+1))
   timeout -s KILL 150 rocprofv3 --pmc $group --kernel-trace -d $O/p$i -o run \
-     --output-format csv -- python3 bench.py $ARGS > $O/p$i.log 2>&1
+     --output-format csv -- python3 bench.py --full $ARGS > $O/p$i.log 2>&1
   rc=$?; echo "pass $i ($group) rc=$rc"
   [ $rc -eq 0 ] || exit $rc
 done <<< "${PMC_GROUPS:-SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD

@@ -9,7 +9,7 @@ for spec in ${SEED_SPECS:-g1000:32:1000}; do
 done
 grep -v amdgpu.ids gpurun_out/seeds.log | tail -5
 if [ -n "$BENCH" ]; then
-  timeout -k 10 300 python -u bench.py --steps 1 --warmup 1 --no-cpu-baseline --n-gen 200 \
+  timeout -k 10 300 python -u bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --n-gen 200 \
     > gpurun_out/bench.json 2> gpurun_out/bench.log || exit 1
   python3 tools/show_bench.py gpurun_out/bench.json
 fi
