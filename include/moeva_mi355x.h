@@ -49,6 +49,15 @@ enum {
   MV_OP_MONTHDIFF = 7,     /* |x[a0] - (month(x[a1]) - month(x[a2]))| lcld_constraints.py:195-201 */
   MV_OP_RATIO_MASKED = 8,  /* |x[a0] - (x[a2]==0|inf|nan ? -1 : x[a1]/x[a2])| lcld:210-216 */
   MV_OP_XOR_AUG = 9,       /* |x[a0] - xor(x[a1]>=k0, x[a2]>=k1)|  examples/utils.py:7-29 */
+  /* tensor-path ops (constraints.evaluate(use_tensors=True), the C-PGD loss; fp32, run by
+   * mv_pgd_* only).  Tensor programs also use DIFF, ABS_SUMDIFF, ABS_RATIO and MONTHDIFF. */
+  MV_OP_TF_INSTALL_MIN = 10,      /* min(|x[a3]-inst(36)|, |x[a3]-inst(60)|) - k0, inst(t) =
+                                     x[a0] r (1+r)^t/((1+r)^t-1), r = x[a2]/1200  lcld:87-105 */
+  MV_OP_TF_HINGE_DIFF = 11,       /* max(k0 + x[a0] - x[a1], 0)            lcld:109-113 */
+  MV_OP_TF_TERM_MIN = 12,         /* min(|36-x[a0]|, |60-x[a0]|)           lcld:116 */
+  MV_OP_TF_RATIO_ALPHA_NEG = 13,  /* |x[a0] - (isnan(x[a1]/x[a2]) ? -1 : x[a1]/(x[a2]+k0))|  lcld:147-151 */
+  MV_OP_TF_RATIO_ALPHA_ZERO = 14, /* isnan(x[a0]-x[a1]) ? 0 : x[a0]/(x[a1]+k0)   botnet:250-269 */
+  MV_OP_TF_ABS_SUMDIFF_OFF = 15,  /* |sum(pool[a0:a1]) - sum(pool[a1:a2])| - k0  botnet:55-75 */
 };
 
 typedef struct mv_problem_desc {
@@ -316,6 +325,58 @@ int mv_debug_survival_dump(double* out);
  * arrays.  Replaces np.power in softmax_mutation.py:77-103 (polynomial mutation) and the
  * SBX option's calc_betaq; oracle/device_order.py:det_pow restates it. */
 int mv_det_pow(int64_t n, const double* x, const double* y, double* out);
+
+/* ---- C-PGD: the constrained gradient attack (src/attacks/pgd/atk.py:74-163 on ART's PGD
+ * loop, src/attacks/pgd/classifier.py:107-332 loss_gradient), whole loop on device.  All
+ * device buffers are fp32; rows are ML-scaled (scaler.transform(x)) unless stated. */
+typedef struct mv_pgd_desc {
+  int32_t D;                  /* ML feature count (== model dims[0]) */
+  const double* ml_scale;     /* host [D] ML MinMaxScaler scale_ (cast to fp32) */
+  const double* ml_min;       /* host [D] min_ */
+  const int32_t* mutable_mask;/* host [D] 1 = mutable */
+  int32_t C;                  /* tensor program: constraint columns */
+  const int32_t* op_code;     /* host [C] MV_OP_* (tensor-path subset) */
+  const int32_t* op_arg;      /* host [C*4] */
+  const double* op_karg;      /* host [C*2] */
+  int32_t n_pool;
+  const int32_t* idx_pool;    /* host [n_pool] */
+  int32_t n_ohe;              /* repair: one-hot groups of the full type mask (0: none) */
+  const int32_t* ohe_offsets; /* host [n_ohe+1] */
+  const int32_t* ohe_feats;
+  int32_t repair_install[4];  /* repair: amount, term, rate, installment features of the LCLD
+                                 formula; repair_install[0] < 0: no formula repair */
+  double tol;                 /* 1e-3 */
+} mv_pgd_desc;
+
+/* loss_flags: which terms the gradient is taken of. */
+enum { MV_PGD_LOSS_FLIP = 1, MV_PGD_LOSS_CONSTRAINTS = 2 };
+
+typedef struct mv_pgd_params {
+  int32_t max_iter;
+  int32_t norm;        /* 2 = L2, 0 = Linf */
+  double eps;
+  double eps_step;
+  int32_t loss_flags;  /* MV_PGD_LOSS_* */
+  int32_t adaptive;    /* eta = eps 10^-(i / (max_iter / 7) + 1); needs max_iter >= 7 */
+  int32_t repair;      /* x = scale(fix_features_types(unscale(x))) after every projection */
+} mv_pgd_params;
+
+typedef struct mv_pgd mv_pgd;
+int mv_pgd_create(int32_t device, const mv_pgd_desc* desc, const mv_model_desc* model,
+                  mv_pgd** out);
+void mv_pgd_destroy(mv_pgd* p);
+/* One loss_gradient: x_scaled dev [n][D], y dev [n] int32 class indices -> grad dev [n][D]
+ * (raw: before mask and normalisation; may be NULL), losses dev [n][2 + C] = (cross-entropy
+ * of the logits, sum of the columns, the C tensor-path columns; may be NULL).  iter is the
+ * attack iteration (the "sum" constraint reduction does not depend on it). */
+int mv_pgd_grad(mv_pgd* p, int32_t n, const float* x_scaled, const int32_t* y,
+                int32_t loss_flags, int32_t iter, float* grad, float* losses, void* stream);
+/* The attack: x_init_scaled dev [n][D] -> x_adv dev [n][D] (the last iterate), one launch.
+ * y dev [n] or NULL (labels = argmax of the model's prediction on x_init_scaled). */
+int mv_pgd_run(mv_pgd* p, const mv_pgd_params* params, int32_t n, const float* x_init_scaled,
+               const int32_t* y, float* x_adv, void* stream);
+/* Constraints.fix_features_types on feature-space (unscaled) rows, in place: dev [n][D]. */
+int mv_pgd_repair(mv_pgd* p, int32_t n, float* x_feature_space, void* stream);
 
 #ifdef __cplusplus
 }

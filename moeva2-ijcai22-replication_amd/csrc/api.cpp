@@ -16,6 +16,7 @@
 #include "detmath.h"
 #include "engine.h"
 #include "kernels.h"
+#include "pgd.h"
 #include "rowops.h"
 
 using namespace mv;
@@ -1821,6 +1822,190 @@ int mv_attack_history(mv_engine* e, double* hist, void* stream) {
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipMemcpyAsync(hist, e->hist, (size_t)e->B * e->hist_rows * e->hist_w * sizeof(double),
                         hipMemcpyDefault, (hipStream_t)stream));
+  return MV_OK;
+}
+
+// ---- C-PGD (pgd.hip)
+struct mv_pgd {
+  int device = 0;
+  PgdArgs a{};
+  std::vector<void*> allocs;
+  ~mv_pgd() {
+    (void)hipSetDevice(device);
+    for (void* x : allocs) (void)hipFree(x);
+  }
+};
+
+int mv_pgd_create(int32_t device, const mv_pgd_desc* d, const mv_model_desc* md, mv_pgd** out) {
+  if (!d || !md || !out) return fail(MV_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (d->D < 1 || d->C < 0 || d->n_ohe < 0 || d->n_pool < 0 || !d->ml_scale || !d->ml_min ||
+      !d->mutable_mask)
+    return fail(MV_ERR_ARG, "mv_pgd_create: bad descriptor");
+  if (md->n_layers < 2 || md->n_layers > PGD_MAX_LAYERS)
+    return fail(MV_ERR_ARG, "mv_pgd_create: 2..6 layers");
+  if (md->dims[0] != d->D) return fail(MV_ERR_ARG, "mv_pgd_create: model input width != D");
+  for (int l = 1; l < md->n_layers; ++l)
+    if (md->dims[l] % 16 != 0 || md->dims[l] < 16 || md->dims[l] > 512)
+      return fail(MV_ERR_ARG, "mv_pgd_create: hidden widths must be multiples of 16 and <= 512");
+  if (md->dims[md->n_layers] < 1 || md->dims[md->n_layers] > PGD_MAX_OUT)
+    return fail(MV_ERR_ARG, "mv_pgd_create: output width must be 1..8");
+  // every index the kernels dereference is checked here
+  auto feat_ok = [&](int f) { return f >= 0 && f < d->D; };
+  for (int i = 0; i < d->n_pool; ++i)
+    if (!feat_ok(d->idx_pool[i])) return fail(MV_ERR_ARG, "mv_pgd_create: pool index out of range");
+  for (int j = 0; j < d->C; ++j) {
+    const int code = d->op_code[j];
+    const int32_t* ar = d->op_arg + 4 * j;
+    int nfeat = 0;
+    bool pooled = false;
+    switch (code) {
+      case MV_OP_DIFF: case MV_OP_TF_HINGE_DIFF: case MV_OP_TF_RATIO_ALPHA_ZERO: nfeat = 2; break;
+      case MV_OP_TF_TERM_MIN: nfeat = 1; break;
+      case MV_OP_ABS_RATIO: case MV_OP_MONTHDIFF: case MV_OP_TF_RATIO_ALPHA_NEG: nfeat = 3; break;
+      case MV_OP_TF_INSTALL_MIN: nfeat = 4; break;
+      case MV_OP_ABS_SUMDIFF: case MV_OP_TF_ABS_SUMDIFF_OFF: pooled = true; break;
+      default:
+        return fail(MV_ERR_ARG, "mv_pgd_create: op " + std::to_string(code) +
+                                    " has no tensor-path form");
+    }
+    for (int k = 0; k < nfeat; ++k)
+      if (!feat_ok(ar[k])) return fail(MV_ERR_ARG, "mv_pgd_create: op feature out of range");
+    if (pooled && !(0 <= ar[0] && ar[0] <= ar[1] && ar[1] <= ar[2] && ar[2] <= d->n_pool))
+      return fail(MV_ERR_ARG, "mv_pgd_create: pool range out of bounds");
+  }
+  if (d->n_ohe > 0) {
+    if (!d->ohe_offsets || !d->ohe_feats || d->ohe_offsets[0] != 0)
+      return fail(MV_ERR_ARG, "mv_pgd_create: bad one-hot groups");
+    for (int g = 0; g < d->n_ohe; ++g)
+      if (d->ohe_offsets[g + 1] <= d->ohe_offsets[g])
+        return fail(MV_ERR_ARG, "mv_pgd_create: empty one-hot group");
+    for (int i = 0; i < d->ohe_offsets[d->n_ohe]; ++i)
+      if (!feat_ok(d->ohe_feats[i])) return fail(MV_ERR_ARG, "mv_pgd_create: one-hot feature out of range");
+  }
+  if (d->repair_install[0] >= 0)
+    for (int k = 0; k < 4; ++k)
+      if (!feat_ok(d->repair_install[k]))
+        return fail(MV_ERR_ARG, "mv_pgd_create: repair feature out of range");
+  HIPCHK(hipSetDevice(device));
+  mv_pgd* p = new mv_pgd();
+  p->device = device;
+  PgdArgs& a = p->a;
+  a.D = d->D;
+  a.C = d->C;
+  a.n_layers = md->n_layers;
+  for (int l = 0; l <= md->n_layers; ++l) a.dims[l] = md->dims[l];
+  a.Dp = d->D | 1;
+  a.tol = (float)d->tol;
+  a.n_ohe = d->n_ohe;
+  for (int k = 0; k < 4; ++k) a.inst[k] = d->repair_install[0] >= 0 ? d->repair_install[k] : -1;
+  // LDS plan: stage the first layer when the weights and one wave's tiles fit
+  a.wpb = 1;
+  a.stage_w0 = 1;
+  if (pgd_lds_bytes(a) > (size_t)PGD_LDS_BYTES) a.stage_w0 = 0;
+  if (pgd_lds_bytes(a) > (size_t)PGD_LDS_BYTES) {
+    delete p;
+    return fail(MV_ERR_ARG, "mv_pgd_create: rows too wide for the LDS tiles");
+  }
+  hipError_t err = hipSuccess;
+  auto K = [&](auto** dst, const auto* host, size_t n) {
+    if (err != hipSuccess) return;
+    err = upload(dst, host, n);
+    if (err == hipSuccess) p->allocs.push_back((void*)*dst);
+  };
+  for (int l = 0; l < a.n_layers; ++l) {
+    K((float**)&a.W[l], md->W[l], (size_t)a.dims[l] * a.dims[l + 1]);
+    K((float**)&a.b[l], md->b[l], (size_t)a.dims[l + 1]);
+  }
+  std::vector<float> sc(d->D), mn(d->D), mk(d->D), ok((size_t)d->C * 2 + 1, 0.f);
+  for (int f = 0; f < d->D; ++f) {
+    sc[f] = (float)d->ml_scale[f];
+    mn[f] = (float)d->ml_min[f];
+    mk[f] = d->mutable_mask[f] ? 1.f : 0.f;
+  }
+  for (int i = 0; i < d->C * 2; ++i) ok[i] = (float)d->op_karg[i];
+  const int32_t zero = 0;
+  K((float**)&a.scale, sc.data(), sc.size());
+  K((float**)&a.minv, mn.data(), mn.size());
+  K((float**)&a.mask, mk.data(), mk.size());
+  K((float**)&a.op_k, ok.data(), ok.size());
+  K((int**)&a.op_code, d->C ? d->op_code : &zero, d->C ? (size_t)d->C : 1);
+  K((int**)&a.op_arg, d->C ? d->op_arg : &zero, d->C ? (size_t)d->C * 4 : 1);
+  K((int**)&a.pool, d->n_pool ? d->idx_pool : &zero, d->n_pool ? (size_t)d->n_pool : 1);
+  K((int**)&a.ohe_off, d->n_ohe ? d->ohe_offsets : &zero, (size_t)d->n_ohe + (d->n_ohe ? 1 : 1));
+  K((int**)&a.ohe_feat, d->n_ohe ? d->ohe_feats : &zero,
+    d->n_ohe ? (size_t)d->ohe_offsets[d->n_ohe] : 1);
+  if (err != hipSuccess) {
+    delete p;
+    return fail(MV_ERR_HIP, std::string("upload: ") + hipGetErrorString(err));
+  }
+  *out = p;
+  return MV_OK;
+}
+
+void mv_pgd_destroy(mv_pgd* p) { delete p; }
+
+int mv_pgd_grad(mv_pgd* p, int32_t n, const float* x, const int32_t* y, int32_t loss_flags,
+                int32_t iter, float* grad, float* losses, void* stream) {
+  (void)iter;
+  if (!p || n < 0 || (n > 0 && (!x || !y))) return fail(MV_ERR_ARG, "bad mv_pgd_grad");
+  if (loss_flags & ~(PGD_LOSS_FLIP | PGD_LOSS_CONSTRAINTS))
+    return fail(MV_ERR_ARG, "mv_pgd_grad: unknown loss flag");
+  if (!on_device(x, p->device) || !on_device(y, p->device) || !on_device(grad, p->device) ||
+      !on_device(losses, p->device))
+    return fail(MV_ERR_ARG, "mv_pgd_grad: a buffer lives on another device than the attack");
+  HIPCHK(hipSetDevice(p->device));
+  PgdArgs a = p->a;
+  a.n = n;
+  a.x_in = x;
+  a.y = y;
+  a.loss_flags = loss_flags;
+  a.grad = grad;
+  a.losses = losses;
+  HIPCHK(launch_pgd_grad(a, (hipStream_t)stream));
+  return MV_OK;
+}
+
+int mv_pgd_run(mv_pgd* p, const mv_pgd_params* prm, int32_t n, const float* x0, const int32_t* y,
+               float* x_adv, void* stream) {
+  if (!p || !prm || n < 0 || (n > 0 && (!x0 || !x_adv))) return fail(MV_ERR_ARG, "bad mv_pgd_run");
+  if (prm->max_iter < 0) return fail(MV_ERR_ARG, "mv_pgd_run: max_iter < 0");
+  if (prm->norm != 2 && prm->norm != 0) return fail(MV_ERR_ARG, "mv_pgd_run: norm 2 or 0 (inf)");
+  if (prm->loss_flags & ~(PGD_LOSS_FLIP | PGD_LOSS_CONSTRAINTS))
+    return fail(MV_ERR_ARG, "mv_pgd_run: unknown loss flag");
+  if (prm->adaptive && prm->max_iter < 7)
+    return fail(MV_ERR_ARG, "mv_pgd_run: adaptive_eps_step needs max_iter >= 7");
+  if (!on_device(x0, p->device) || !on_device(y, p->device) || !on_device(x_adv, p->device))
+    return fail(MV_ERR_ARG, "mv_pgd_run: a buffer lives on another device than the attack");
+  HIPCHK(hipSetDevice(p->device));
+  PgdArgs a = p->a;
+  a.n = n;
+  a.x_in = x0;
+  a.y = y;
+  a.x_out = x_adv;
+  a.max_iter = prm->max_iter;
+  a.norm = prm->norm;
+  a.loss_flags = prm->loss_flags;
+  a.adaptive = prm->adaptive ? 1 : 0;
+  a.repair = prm->repair ? 1 : 0;
+  a.eps = (float)prm->eps;
+  a.eps_step = (float)prm->eps_step;
+  a.iter_per_step = prm->adaptive ? prm->max_iter / 7 : 1;
+  // atk.py:129-132: eps * (1 / float_power(10, i // (max_iter // 7) + 1)) in fp64, then fp32
+  for (int k = 0; k < PGD_ETA_TAB; ++k)
+    a.eta_tab[k] = (float)(prm->eps * (1.0 / std::pow(10.0, (double)(k + 1))));
+  HIPCHK(launch_pgd(a, (hipStream_t)stream));
+  return MV_OK;
+}
+
+int mv_pgd_repair(mv_pgd* p, int32_t n, float* x, void* stream) {
+  if (!p || n < 0 || (n > 0 && !x)) return fail(MV_ERR_ARG, "bad mv_pgd_repair");
+  if (!on_device(x, p->device))
+    return fail(MV_ERR_ARG, "mv_pgd_repair: x lives on another device than the attack");
+  HIPCHK(hipSetDevice(p->device));
+  PgdArgs a = p->a;
+  a.n = n;
+  HIPCHK(launch_pgd_repair(a, x, (hipStream_t)stream));
   return MV_OK;
 }
 

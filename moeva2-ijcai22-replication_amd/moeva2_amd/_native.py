@@ -18,7 +18,10 @@ LIB_PATH = os.environ.get("MOEVA_MI355X_LIB", os.path.join(PKG_ROOT, "lib", "lib
 
 MV_GENE_REAL, MV_GENE_INT, MV_GENE_OHE = 0, 1, 2
 OP = dict(DIFF=1, RATIO_SAFE=2, ABS_SUMDIFF=3, LCLD_INSTALL=4, LCLD_TERM=5, ABS_RATIO=6,
-          MONTHDIFF=7, RATIO_MASKED=8, XOR_AUG=9)
+          MONTHDIFF=7, RATIO_MASKED=8, XOR_AUG=9,
+          # tensor-path ops (C-PGD; mv_pgd_* only)
+          TF_INSTALL_MIN=10, TF_HINGE_DIFF=11, TF_TERM_MIN=12, TF_RATIO_ALPHA_NEG=13,
+          TF_RATIO_ALPHA_ZERO=14, TF_ABS_SUMDIFF_OFF=15)
 
 EXPORTED = [
     "mv_last_error", "mv_device_count", "mv_engine_create", "mv_engine_destroy",
@@ -32,6 +35,7 @@ EXPORTED = [
     "mv_mlp_predict", "mv_objcalc_create", "mv_objcalc_destroy", "mv_objcalc_run",
     "mv_objcalc_score", "mv_det_pow", "mv_debug_checks", "mv_set_state_streams",
     "mv_debug_survival_dump", "mv_get_stored_genes", "mv_gene_layout", "mv_set_gene_layout",
+    "mv_pgd_create", "mv_pgd_destroy", "mv_pgd_grad", "mv_pgd_run", "mv_pgd_repair",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -65,6 +69,23 @@ class ObjCalcDesc(C.Structure):
     _fields_ = [("D", C.c_int32), ("n_ohe", C.c_int32), ("ohe_offsets", _i32p),
                 ("ohe_feats", _i32p), ("mm_scale", _f64p), ("mm_min", _f64p),
                 ("ml_scale", _f64p), ("ml_min", _f64p), ("norm", C.c_int32)]
+
+
+class PgdDesc(C.Structure):
+    _fields_ = [("D", C.c_int32), ("ml_scale", _f64p), ("ml_min", _f64p),
+                ("mutable_mask", _i32p), ("C", C.c_int32), ("op_code", _i32p), ("op_arg", _i32p),
+                ("op_karg", _f64p), ("n_pool", C.c_int32), ("idx_pool", _i32p),
+                ("n_ohe", C.c_int32), ("ohe_offsets", _i32p), ("ohe_feats", _i32p),
+                ("repair_install", C.c_int32 * 4), ("tol", C.c_double)]
+
+
+class PgdParams(C.Structure):
+    _fields_ = [("max_iter", C.c_int32), ("norm", C.c_int32), ("eps", C.c_double),
+                ("eps_step", C.c_double), ("loss_flags", C.c_int32), ("adaptive", C.c_int32),
+                ("repair", C.c_int32)]
+
+
+PGD_LOSS_FLIP, PGD_LOSS_CONSTRAINTS = 1, 2
 
 
 class NativeError(RuntimeError):
@@ -123,6 +144,10 @@ def lib():
             "mv_get_stored_genes": [vp, _i32p, _i32p],
             "mv_gene_layout": [vp, C.c_int32, _f64p, _f64p, _f64p, _i32p, _i32p],
             "mv_set_gene_layout": [vp, _i32p, C.c_int32],
+            "mv_pgd_create": [C.c_int32, C.POINTER(PgdDesc), C.POINTER(ModelDesc), C.POINTER(vp)],
+            "mv_pgd_grad": [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp],
+            "mv_pgd_run": [vp, C.POINTER(PgdParams), C.c_int32, vp, vp, vp, vp],
+            "mv_pgd_repair": [vp, C.c_int32, vp, vp],
         }
         for name, args in sig.items():
             try:
@@ -137,6 +162,8 @@ def lib():
         L.mv_mlp_destroy.restype = None
         L.mv_objcalc_destroy.argtypes = [vp]
         L.mv_objcalc_destroy.restype = None
+        L.mv_pgd_destroy.argtypes = [vp]
+        L.mv_pgd_destroy.restype = None
         _LIB = L
     return _LIB
 
@@ -552,6 +579,75 @@ class ObjCalc:
         check(lib().mv_objcalc_score(self._h, B, n, _ptr(x_init), _ptr(x), _ptr(G), C_,
                                      _ptr(proba), int(proba.shape[-1]), int(minimize_class),
                                      _ptr(obj), _ptr(range_bad), _stream(stream)))
+
+
+class Pgd:
+    """Device C-PGD (mv_pgd_*): one per (device, tensor program, scaler, classifier).
+
+    ``program`` is a ConstraintProgram built by ``Constraints.tensor_program()``;
+    ``ohe_groups`` / ``repair_install`` describe ``fix_features_types`` (empty / None: the
+    identity)."""
+
+    def __init__(self, program, weights, biases, ml_scale, ml_min, mutable_mask,
+                 ohe_groups=(), repair_install=None, tol=1e-3, device=0):
+        keep = []
+
+        def P(a, dt, ct):
+            a = np.ascontiguousarray(a, dt)
+            keep.append(a)
+            return a.ctypes.data_as(C.POINTER(ct))
+
+        code, arg, karg, pool = program.arrays()
+        d = PgdDesc()
+        d.D = int(np.asarray(ml_scale).shape[0])
+        d.ml_scale = P(ml_scale, np.float64, C.c_double)
+        d.ml_min = P(ml_min, np.float64, C.c_double)
+        d.mutable_mask = P(np.asarray(mutable_mask).astype(bool), np.int32, C.c_int32)
+        d.C = int(code.shape[0])
+        d.op_code = P(code if code.size else np.zeros(1), np.int32, C.c_int32)
+        d.op_arg = P(arg if arg.size else np.zeros(4), np.int32, C.c_int32)
+        d.op_karg = P(karg if karg.size else np.zeros(2), np.float64, C.c_double)
+        d.n_pool = int(pool.shape[0])
+        d.idx_pool = P(pool if pool.size else np.zeros(1), np.int32, C.c_int32)
+        offs = np.zeros(len(ohe_groups) + 1, np.int32)
+        for g, m in enumerate(ohe_groups):
+            offs[g + 1] = offs[g] + len(m)
+        feats = (np.concatenate([np.asarray(m, np.int32) for m in ohe_groups])
+                 if len(ohe_groups) else np.zeros(1, np.int32))
+        d.n_ohe = len(ohe_groups)
+        d.ohe_offsets = P(offs, np.int32, C.c_int32)
+        d.ohe_feats = P(feats, np.int32, C.c_int32)
+        ri = list(repair_install) if repair_install is not None else [-1, -1, -1, -1]
+        d.repair_install = (C.c_int32 * 4)(*[int(v) for v in ri])
+        d.tol = float(tol)
+        md = _model_desc(weights, biases, keep)
+        self._h = C.c_void_p()
+        check(lib().mv_pgd_create(device, C.byref(d), C.byref(md), C.byref(self._h)))
+        self.device = device
+        self.D = d.D
+        self.C = d.C
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _LIB is not None:
+            _LIB.mv_pgd_destroy(h)
+            self._h = None
+
+    def grad(self, x, y, loss_flags, grad=None, losses=None, iter_i=0, stream=None):
+        """x (n, D) fp32, y (n,) int32 device tensors -> grad (n, D), losses (n, 2 + C)."""
+        check(lib().mv_pgd_grad(self._h, int(x.shape[0]), _ptr(x), _ptr(y), int(loss_flags),
+                                int(iter_i), _ptr(grad), _ptr(losses), _stream(stream)))
+
+    def run(self, x_init, x_adv, max_iter, norm, eps, eps_step, loss_flags, adaptive=False,
+            repair=False, y=None, stream=None):
+        prm = PgdParams(int(max_iter), norm_code(norm), float(eps), float(eps_step),
+                        int(loss_flags), int(bool(adaptive)), int(bool(repair)))
+        check(lib().mv_pgd_run(self._h, C.byref(prm), int(x_init.shape[0]), _ptr(x_init),
+                               _ptr(y), _ptr(x_adv), _stream(stream)))
+
+    def repair(self, x, stream=None):
+        """fix_features_types on feature-space rows x (n, D) fp32, in place."""
+        check(lib().mv_pgd_repair(self._h, int(x.shape[0]), _ptr(x), _stream(stream)))
 
 
 _MLPS = {}

@@ -34,12 +34,12 @@ class ConstraintProgram:
         self.arg.append([int(v) for v in a])
         self.karg.append([float(v) for v in k])
 
-    def add_sumdiff(self, first: List[int], second: List[int]):
+    def add_sumdiff(self, first: List[int], second: List[int], op: str = "ABS_SUMDIFF", k=()):
         o0 = len(self.pool)
         self.pool.extend(int(v) for v in first)
         o1 = len(self.pool)
         self.pool.extend(int(v) for v in second)
-        self.add("ABS_SUMDIFF", (o0, o1, len(self.pool)))
+        self.add(op, (o0, o1, len(self.pool)), k)
 
     def arrays(self):
         return (np.asarray(self.code, np.int32), np.asarray(self.arg, np.int32).reshape(-1, 4),
@@ -88,6 +88,13 @@ class Constraints(abc.ABC, metaclass=abc.ABCMeta):
         raise NotImplementedError(
             f"{type(self).__name__} has no device constraint program; the MI355X engine "
             "evaluates constraints only through device programs")
+
+    def tensor_program(self) -> ConstraintProgram:
+        """The tensor path of ``evaluate`` (``use_tensors=True``, the C-PGD constraint loss)
+        as a device program (engine extension)."""
+        raise NotImplementedError(
+            f"{type(self).__name__} has no tensor-path constraint program (C-PGD covers the "
+            "LCLD and botnet classes)")
 
     def check_constraints_error(self, x: np.ndarray):
         """constraints.py:73-77."""
@@ -150,8 +157,53 @@ class TabularConstraints(Constraints):
     def get_nb_constraints(self) -> int:
         return len(self.device_program())
 
+    def tensor_repair(self):
+        """What ``fix_features_types`` does, for the device: (one-hot groups, the four
+        features of the LCLD installment formula or None).  Default: the identity."""
+        return [], None
+
+    def _tensor_engine(self, device=None):
+        """The C-PGD engine in feature space (identity scaler, a null classifier) behind
+        ``evaluate(use_tensors=True)`` and ``fix_features_types``; one per device."""
+        import torch
+
+        from ..._native import Pgd
+
+        prog = self.tensor_program()  # NotImplementedError for classes without one
+        dev = torch.cuda.current_device() if device is None else int(device)
+        engines = self.__dict__.setdefault("_tensor_engines", {})
+        eng = engines.get(dev)
+        if eng is None:
+            D = self._feature_type.shape[0]
+            groups, install = self.tensor_repair()
+            eng = engines[dev] = Pgd(
+                prog, [np.zeros((D, 16), np.float32), np.zeros((16, 2), np.float32)],
+                [np.zeros(16, np.float32), np.zeros(2, np.float32)], np.ones(D), np.zeros(D),
+                np.asarray(self._mutable_mask).astype(bool), groups, install, tol=self.tol,
+                device=dev)
+        return eng
+
     def fix_features_types(self, x):
-        raise NotImplementedError("TensorFlow repair path (C-PGD) is out of scope")
+        """lcld_constraints.py:40-73 on the device (mv_pgd_repair): float32 rows back."""
+        import torch
+
+        eng = self._tensor_engine()
+        xd = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(x), np.float32)).cuda(eng.device)
+        eng.repair(xd, stream=torch.cuda.current_stream(xd.device))
+        return xd.cpu().numpy()
+
+    def _evaluate_tensor_path(self, x) -> np.ndarray:
+        import torch
+
+        from ..._native import PGD_LOSS_CONSTRAINTS
+
+        eng = self._tensor_engine()
+        xd = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(x), np.float32)).cuda(eng.device)
+        y = torch.zeros(xd.shape[0], dtype=torch.int32, device=xd.device)
+        losses = torch.empty((xd.shape[0], 2 + eng.C), dtype=torch.float32, device=xd.device)
+        eng.grad(xd, y, PGD_LOSS_CONSTRAINTS, None, losses,
+                 stream=torch.cuda.current_stream(xd.device))
+        return losses[:, 2:].cpu().numpy()
 
     def get_feature_min_max(self, dynamic_input=None):
         """lcld_constraints.py:237-263: 'dynamic' bounds come from the input."""
@@ -215,7 +267,7 @@ class TabularConstraints(Constraints):
 
     def evaluate(self, x: np.ndarray, use_tensors: bool = False) -> np.ndarray:
         if use_tensors:
-            raise NotImplementedError("TensorFlow evaluation path (C-PGD) is out of scope")
+            return self._evaluate_tensor_path(x)
         import torch
 
         x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)

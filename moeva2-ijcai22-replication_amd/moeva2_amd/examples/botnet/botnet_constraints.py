@@ -40,6 +40,32 @@ def botnet_program(prog: ConstraintProgram, feat_idx: dict) -> ConstraintProgram
     return prog
 
 
+def botnet_tensor_program(prog: ConstraintProgram, feat_idx: dict,
+                          alpha: float = 1e-5) -> ConstraintProgram:
+    """evaluate_tf2 (botnet_constraints.py:48-115, 235-269): g1 carries the - 0.4999999
+    offset, the packet / byte block is a / (b + alpha) without the - 1500 (17 ports per
+    direction, the same loop bound as the numpy path), the DIFF columns are unchanged."""
+    fi = feat_idx
+    for d, off in (("s", 0.4999999), ("d", 0.0)):
+        first = fi[f"icmp_sum_{d}_idx"] + fi[f"udp_sum_{d}_idx"] + fi[f"tcp_sum_{d}_idx"]
+        second = fi[f"bytes_in_sum_{d}_idx"] + fi[f"bytes_out_sum_{d}_idx"]
+        if off:
+            prog.add_sumdiff(first, second, "TF_ABS_SUMDIFF_OFF", (off,))
+        else:
+            prog.add_sumdiff(first, second)
+    for bo, po in (("bytes_out_sum_s_idx", "pkts_out_sum_s_idx"),
+                   ("bytes_out_sum_d_idx", "pkts_out_sum_d_idx")):
+        for j in range(len(bo) - 2):
+            prog.add("TF_RATIO_ALPHA_ZERO", (fi[bo][j], fi[po][j]), (alpha,))
+    keys = list(fi.keys())
+    for upper, lower in ((SUM_IDX, MAX_IDX), (SUM_IDX, MIN_IDX), (MAX_IDX, MIN_IDX)):
+        for i in range(len(upper)):
+            up_k, lo_k = keys[upper[i]], keys[lower[i]]
+            for j in range(len(fi[keys[upper[i]]])):
+                prog.add("DIFF", (fi[lo_k][j], fi[up_k][j]))
+    return prog
+
+
 def load_feat_idx(feature_path: str) -> dict:
     with open(_resolve(feature_path, "feat_idx.json")) as f:
         return json.load(f)
@@ -57,6 +83,9 @@ class BotnetConstraints(TabularConstraints):
 
     def device_program(self) -> ConstraintProgram:
         return botnet_program(ConstraintProgram(), self.feat_idx)
+
+    def tensor_program(self) -> ConstraintProgram:
+        return botnet_tensor_program(ConstraintProgram(), self.feat_idx)
 
     def get_nb_constraints(self) -> int:
         return 360
