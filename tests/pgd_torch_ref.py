@@ -88,13 +88,18 @@ def botnet_tf(x, fi):
 class Spec:
     """One project's attack in torch: weights, scaler, mask, constraint function."""
 
-    def __init__(self, project, dtype=torch.float32):
+    def __init__(self, project, dtype=torch.float32, weights=None, biases=None):
+        """weights / biases: an explicit Dense MLP (fp32 arrays, relu ... softmax) in place
+        of the shipped nn.npz."""
         self.project, self.dtype = project, dtype
-        d = np.load(os.path.join(RES, "models", project, "nn.npz"), allow_pickle=False)
-        n = sum(1 for k in d.files if k.startswith("W"))
+        if weights is None:
+            d = np.load(os.path.join(RES, "models", project, "nn.npz"), allow_pickle=False)
+            n = sum(1 for k in d.files if k.startswith("W"))
+            weights = [d[f"W{i}"] for i in range(n)]
+            biases = [d[f"b{i}"] for i in range(n)]
         # weights and scaler are fp32 values (what the device holds), widened for fp64
-        self.W = [torch.tensor(d[f"W{i}"].astype(np.float32)).to(dtype) for i in range(n)]
-        self.b = [torch.tensor(d[f"b{i}"].astype(np.float32)).to(dtype) for i in range(n)]
+        self.W = [torch.tensor(np.asarray(w).astype(np.float32)).to(dtype) for w in weights]
+        self.b = [torch.tensor(np.asarray(b).astype(np.float32)).to(dtype) for b in biases]
         sc = np.load(os.path.join(RES, "models", project, "scaler.npz"), allow_pickle=False)
         self.scale = torch.tensor(sc["scale_"].astype(np.float32)).to(dtype)
         self.min = torch.tensor(sc["min_"].astype(np.float32)).to(dtype)
@@ -172,9 +177,11 @@ class Spec:
             x = self.rescale(self.repair(self.unscale(x), ohe_groups))
         return x
 
-    def attack(self, x_init, mask, mode, norm, eps, max_iter, eps_step=0.1, ohe_groups=()):
+    def attack(self, x_init, mask, mode, norm, eps, max_iter, eps_step=0.1, ohe_groups=(),
+               y=None):
+        """y: labels (n,); None: the model's own prediction on x_init."""
         x_init = torch.as_tensor(x_init, dtype=self.dtype)
-        y = self.predict(x_init)
+        y = self.predict(x_init) if y is None else torch.as_tensor(np.asarray(y), dtype=torch.long)
         x = x_init.clone()
         for i in range(max_iter):
             g = self.grad(x, y, mode)[0]
