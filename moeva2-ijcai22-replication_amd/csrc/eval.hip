@@ -2180,8 +2180,14 @@ __host__ __device__ inline Mw32Lds mlpw32_lds(const DProblem& p) {
   const unsigned head =
       256 + (((unsigned)(p.dims[nl - 1] * p.dims[nl] + p.dims[nl]) * 4 + 15) & ~15u);
   L.h = head;
-  L.part = L.h + (unsigned)MW_ROWS * L.hs * 4;
-  L.total = L.part + (unsigned)(MW_T / 64) * MW_ROWS * p.dims[nl] * 4;
+  // the wave partials of the final Dense alias the activation buffer: they are written after
+  // the barrier that retires the last MFMA layer's reads of it, and that layer's outputs stay
+  // in registers (a separate region put 512-wide nets of 8 classes past the CU's LDS and onto
+  // the 32-row-tile k_mlp)
+  L.part = L.h;
+  const unsigned hb = (unsigned)MW_ROWS * L.hs * 4;
+  const unsigned pb = (unsigned)(MW_T / 64) * MW_ROWS * p.dims[nl] * 4;
+  L.total = L.h + (hb > pb ? hb : pb);
   return L;
 }
 // The shapes k_mlpw32 takes: every MFMA layer's K and N multiples of 16 (Wp packed), at

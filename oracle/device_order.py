@@ -20,6 +20,11 @@ and the device attack can be compared trajectory for trajectory:
   One fp32 fmaf is restated as round32(a * b + c) evaluated in fp64, where a * b
   is exact; the fp64 rounding of the sum can differ from the fused single rounding only if
   it lands exactly on an fp32 midpoint (probability ~2^-29 per operation).
+  k_mlpr sums in the same order.  k_mlpw32 (fp32 hidden widths above 128;
+  ``kernel="mlpw32"``) shares the layer-0 bias and the MFMA hidden layers and differs in
+  the last Dense layer only: wave w of 8 keeps the last hidden layer's column tiles w + 8 j
+  in registers, lane il chains fmaf over j, the 16 lanes are combined by the
+  xor-1,2,4,8 butterfly, the 8 wave partials are added in wave order from 0.f, then the bias.
 * f2: each of 64 lanes sums the squared distances of features lane + 64 t in order, the 64
   partial sums are combined by the wave's butterfly (a balanced pairwise tree in lane
   order), then sqrt and the scale (default_problem.py:80-91).
@@ -231,7 +236,51 @@ def layer0_bias(prob: "mo.Problem", fixed=None):
     return (prob.biases[0].astype(np.float32) + s).astype(np.float32)
 
 
-def f1_device_order(prob: "mo.Problem", x_f: np.ndarray, fixed=None) -> np.ndarray:
+def mlpw32_cj(prob):
+    """launch_mlp's k_mlpw32 instance: column tiles per wave by the widest hidden layer."""
+    hm = max(w.shape[1] for w in prob.weights[:-1])
+    return 1 if hm <= 128 else 2 if hm <= 256 else 4
+
+
+def _last_dense_mlp2(h, W):
+    """k_mlp2 / k_mlpr: wave w's fmaf chain over the k quarter [w K/4, (w+1) K/4), the four
+    quarters combined ((q0 + q1) + q2) + q3."""
+    kq = W.shape[0] // 4
+    q = []
+    for w in range(4):
+        ps = np.zeros((h.shape[0], W.shape[1]), np.float32)
+        for k in range(w * kq, (w + 1) * kq):
+            ps = _fma32(h[:, k:k + 1], W[k][None, :], ps)
+        q.append(ps)
+    return ((q[0] + q[1]) + q[2]) + q[3]
+
+
+def _last_dense_mlpw32(h, W, cj):
+    """k_mlpw32: the last hidden layer stays in the MFMA accumulators, so lane il of wave w
+    holds columns (w + 8 j) 16 + il of its up to ``cj`` column tiles: an fmaf chain over j
+    from 0.f (tiles past the layer's width skipped), the 16 lanes combined by the xor-1,2,4,8
+    butterfly (wave_tree on 16 columns), the 8 wave partials added in wave order from 0.f."""
+    n, (K, nout) = h.shape[0], W.shape
+    nct = K // 16
+    z = np.zeros((n, nout), np.float32)
+    for w in range(8):
+        ps = np.zeros((n, 16, nout), np.float32)
+        for j in range(cj):
+            ct = w + 8 * j
+            if ct < nct:
+                c0 = 16 * ct
+                ps = _fma32(h[:, c0:c0 + 16, None], W[None, c0:c0 + 16, :], ps)
+        part = np.stack([wave_tree(ps[:, :, c]) for c in range(nout)], axis=1)
+        z = z + part.astype(np.float32)
+    return z
+
+
+def f1_device_order(prob: "mo.Problem", x_f: np.ndarray, fixed=None,
+                    kernel="mlp2") -> np.ndarray:
+    """``kernel``: "mlp2" (k_mlp2 and k_mlpr: the same order) or "mlpw32" (the fp32 wide
+    classifier: the same layer-0 bias and MFMA hidden layers, its own last Dense)."""
+    if kernel not in ("mlp2", "mlpw32"):
+        raise ValueError(f"kernel {kernel!r}: 'mlp2' or 'mlpw32'")
     mut = np.where(_mutable(prob, fixed))[0]
     x_ml = x_f if prob.ml_scale is None else mo.minmax_transform(x_f, prob.ml_scale, prob.ml_min)
     Dm = mut.size
@@ -247,15 +296,11 @@ def f1_device_order(prob: "mo.Problem", x_f: np.ndarray, fixed=None) -> np.ndarr
         h = np.maximum(_dense_mfma(h, W, W.shape[0]) + prob.biases[l].astype(np.float32),
                        np.float32(0))
     W = prob.weights[nl - 1].astype(np.float32)
-    Kl = W.shape[0]
-    kq = Kl // 4
-    q = []
-    for w in range(4):
-        ps = np.zeros((h.shape[0], W.shape[1]), np.float32)
-        for k in range(w * kq, (w + 1) * kq):
-            ps = _fma32(h[:, k:k + 1], W[k][None, :], ps)
-        q.append(ps)
-    z = ((((q[0] + q[1]) + q[2]) + q[3]) + prob.biases[nl - 1].astype(np.float32))
+    if kernel == "mlpw32":
+        z = _last_dense_mlpw32(h, W, mlpw32_cj(prob))
+    else:
+        z = _last_dense_mlp2(h, W)
+    z = z + prob.biases[nl - 1].astype(np.float32)
     return softmax_keras32(z)[:, prob.minimize_class].astype(np.float64)
 
 
@@ -325,12 +370,13 @@ def f3_device_order(G: np.ndarray, op_codes) -> np.ndarray:
 
 
 def evaluate_device_order(prob: "mo.Problem", genes: np.ndarray, op_codes, return_g=False,
-                          fixed=None):
+                          fixed=None, kernel="mlp2"):
     """``moeva_oracle.evaluate`` with the engine's summation orders (module docstring);
-    ``fixed``: the attack's compact layout (features evaluated as immutable)."""
+    ``fixed``: the attack's compact layout (features evaluated as immutable); ``kernel``:
+    the classifier kernel whose order f1 takes (f1_device_order)."""
     x_f = mo.genetic_to_ml(prob.lay, genes, prob.x_init)
     g = prob.constraints_fn(x_f)
     g = g * (g > 0).astype(np.float64)
-    F = np.column_stack([f1_device_order(prob, x_f, fixed), f2_device_order(prob, x_f, fixed),
+    F = np.column_stack([f1_device_order(prob, x_f, fixed, kernel), f2_device_order(prob, x_f, fixed),
                          f3_device_order(g, op_codes)])
     return (F, g) if return_g else F

@@ -15,9 +15,11 @@ offset arithmetic at these B.  For each:
     (configs[2] / [3]: final genes, f1, f2 and the history's f1 / f2 bit-identical; f3 and
     G to 1e-12 relative: the device's pow in the LCLD installment identity is its libm's,
     the restatement's np.power); configs[4]'s 512-wide
-    classifier runs k_mlp, whose summation order the engine-order restatement does not
-    cover, so there the picked states' final F is checked against the oracle's evaluation in
-    the reference's arithmetic (f1 1e-5 relative, f2 / f3 1e-12: north_star's tolerances).
+    classifier runs k_mlpw32, restated as device_order's ``kernel="mlpw32"``: the picked
+    states' final genes, f1 and f2 bit-identical to that order's attack in the compact gene
+    layout and f3 exact (botnet constraints call no pow), and their final F also against the
+    oracle's evaluation in the reference's arithmetic (f1 1e-5 relative, f2 / f3 1e-12:
+    north_star's tolerances).
 Reference shapes: config/rq4.lcld.moeva_augmented.yaml:12-14 (4,000 states),
 src/attacks/moeva2/moeva2.py:44-46 (the 640 / 320 defaults of configs[3])."""
 import dataclasses
@@ -99,9 +101,11 @@ def run(workload, X, n_gen, hist):
     return eng, c, g, F, h
 
 
-def oracle_attack(workload, project, c, X, picks, n_gen, hist):
+def oracle_attack(workload, project, c, X, picks, n_gen, hist, fixed=None, kernel="mlp2"):
     """The engine-order oracle attack (oracle/device_order.py: the engine's summation orders
-    and det_pow; moeva_oracle.run_attack: the same Philox draws) of the picked states."""
+    and det_pow; moeva_oracle.run_attack: the same Philox draws) of the picked states, with
+    the workload's synthetic classifier if it has one; ``fixed`` / ``kernel``: the compact
+    gene layout and the classifier kernel whose order f1 takes (evaluate_device_order)."""
     import bench
     from moeva2_amd.attacks.moeva2.ref_dirs import energy_ref_dirs
     from moeva2_amd.problem import build_device_program
@@ -113,15 +117,21 @@ def oracle_attack(workload, project, c, X, picks, n_gen, hist):
     ref = energy_ref_dirs(3, w["n_pop"], seed=1)
 
     def ev(prob, genes, return_g=False):
-        return do.evaluate_device_order(prob, genes, codes, return_g)
+        return do.evaluate_device_order(prob, genes, codes, return_g, fixed=fixed, kernel=kernel)
+
+    def problem(x):
+        prob = p.problem(x, norm=w["norm"])
+        if w["model"].startswith("synthetic:"):
+            m = bench.synthetic_mlp(w["model"])
+            prob = dataclasses.replace(prob, weights=m.weights, biases=m.biases)
+        return prob
 
     mode = {0: None, 1: "reduced", 2: "full"}[hist]
-    return [mo.run_attack(p.problem(X[b], norm=w["norm"]), ref, n_gen, w["n_pop"] + 3,
-                          w["n_off"], 42, save_history=mode, evaluate_fn=ev,
-                          pow_fn=do.det_pow) for b in picks]
+    return [mo.run_attack(problem(X[b]), ref, n_gen, w["n_pop"] + 3, w["n_off"], 42,
+                          save_history=mode, evaluate_fn=ev, pow_fn=do.det_pow) for b in picks]
 
 
-def check_full(workload, project, n_states, n_gen, hist, compact, pin="attack"):
+def check_full(workload, project, n_states, n_gen, hist, compact, pin="attack", kernel="mlp2"):
     import bench
 
     X = bench.load_states(dict(bench.WORKLOADS[workload], n_states=n_states))
@@ -184,6 +194,14 @@ def check_full(workload, project, n_states, n_gen, hist, compact, pin="attack"):
             ref = mo.evaluate(prob, gs[k])
             np.testing.assert_allclose(Fs[k][:, 0], ref[:, 0], rtol=1e-5, atol=1e-7)
             np.testing.assert_allclose(Fs[k][:, 1:], ref[:, 1:], rtol=1e-12, atol=1e-15)
+        # and the trajectory, in the compact layout the full-size run used
+        stored = eng.stored_genes()
+        fixed = np.zeros(p.lay.mutable_mask.shape[0], bool)
+        fixed[np.where(p.lay.mutable_mask)[0][~stored]] = True
+        for k, r in enumerate(oracle_attack(workload, project, c, X, pick, n_gen, hist,
+                                            fixed=fixed, kernel=kernel)):
+            np.testing.assert_array_equal(gs[k], r.pop_X)
+            np.testing.assert_array_equal(Fs[k], r.pop_F)
     return eng
 
 
@@ -201,8 +219,10 @@ def test_configs2_augmented_full_history():
 
 
 def test_configs4_wide_mlp_full_state_count():
-    """configs[4]: 10,000 botnet-shaped states with the 756-512-512-256-2 MLP (k_mlp), 3
-    generations, compact gene layout."""
+    """configs[4]: 10,000 botnet-shaped states with the 756-512-512-256-2 MLP (k_mlpw32), 3
+    generations, compact gene layout; the picked states' trajectories pinned to the oracle's
+    attack in k_mlpw32's evaluation order."""
     eng = check_full("synthetic.botnet.wide", "botnet", 10000, 3, 0, compact=True,
-                     pin="evaluate")
+                     pin="evaluate", kernel="mlpw32")
+    assert eng.kernel_times()["mlp_kernel"] == "k_mlpw32"
     assert (~eng.stored_genes()).sum() == 120

@@ -195,27 +195,39 @@ def test_row_classifier_shapes_bit_exact(dims):
         np.testing.assert_array_equal(Fa[b], ref)
 
 
-def _wide_mlp(dims=(756, 512, 512, 256, 2), seed=7):
-    """bench.py's configs[4] classifier: Dense relu x3 + softmax, weights ~ N(0, 1/fan_in)."""
+def _wide_mlp(dims=(756, 512, 512, 256, 2), seed=7, bias_scale=0.0):
+    """bench.py's configs[4] classifier: Dense relu x3 + softmax, weights ~ N(0, 1/fan_in),
+    zero biases (``bias_scale`` > 0: biases bias_scale * N(0, 1) from a stream of their own,
+    the weights unchanged)."""
     rng = np.random.default_rng(seed)
     W = [(rng.standard_normal((a, b)) / np.sqrt(a)).astype(np.float32)
          for a, b in zip(dims[:-1], dims[1:])]
-    return W, [np.zeros(b, np.float32) for b in dims[1:]]
+    if not bias_scale:
+        return W, [np.zeros(b, np.float32) for b in dims[1:]]
+    rng = np.random.default_rng([seed, 1])
+    return W, [(bias_scale * rng.standard_normal(b)).astype(np.float32) for b in dims[1:]]
 
 
 def test_wide_mlp_config_matches_fp32_reference():
-    """BASELINE configs[4] (synthetic.botnet.wide: 756-512-512-256-2) runs the 64-row-tile
-    k_mlpw32 path (fp32 hidden widths > 128) in the attack and k_predict in predict_proba: f1
-    of mv_evaluate and of Classifier.predict_proba against the fp32 numpy forward (1e-5 rel),
-    f2/f3 unchanged, then a short attack keeps its invariants and is deterministic."""
+    """BASELINE configs[4] (synthetic.botnet.wide: 756-512-512-256-2, here with non-zero biases
+    in every layer) runs the 64-row-tile k_mlpw32 path (fp32 hidden widths > 128) in the attack
+    and k_predict in predict_proba: f1 of mv_evaluate and of Classifier.predict_proba against
+    the fp32 numpy forward (1e-5 rel), f2/f3 unchanged, and mv_evaluate's F bit-identical to
+    oracle/device_order's k_mlpw32 order; then a short attack keeps its invariants, is
+    deterministic, and its final F is bit-identical to that order in the compact layout."""
+    import dataclasses
+
+    from oracle import device_order as do
     from moeva2_amd.attacks.moeva2.classifier import Classifier, DenseMLPModel
     from moeva2_amd.io.tf_bundle import DenseMLP
-    from moeva2_amd.problem import get_engine
+    from moeva2_amd.problem import build_device_program, get_engine
 
     p = Project("botnet")
-    W, bs = _wide_mlp()
+    W, bs = _wide_mlp(bias_scale=0.1)
+    assert all(np.abs(b).min() > 0 for b in bs)
     clf = Classifier(DenseMLPModel(DenseMLP(W, bs, ["relu"] * 3 + ["softmax"])))
     c, sc = make_constraints("botnet"), make_scaler("botnet")
+    codes = build_device_program(c).op_code
     X = p.x[:6]
     xm = X * p.ml[0] + p.ml[1]
     ref_p = mo.mlp_predict_proba(xm, W, bs)
@@ -245,6 +257,11 @@ def test_wide_mlp_config_matches_fp32_reference():
         np.testing.assert_allclose(F[b, :, 0], f1, rtol=1e-5, atol=1e-7)
         ref = mo.evaluate(p.problem(X[b]), genes[b])
         np.testing.assert_allclose(F[b, :, 1:], ref[:, 1:], rtol=1e-12, atol=1e-15)
+    probs = [dataclasses.replace(p.problem(X[b]), weights=W, biases=bs)
+             for b in range(X.shape[0])]
+    for b in range(X.shape[0]):
+        ref = do.evaluate_device_order(probs[b], genes[b], codes, kernel="mlpw32")
+        np.testing.assert_array_equal(F[b], ref)
     from moeva2_amd.attacks.moeva2.ref_dirs import riesz_energy_dirs
 
     ref_dirs = riesz_energy_dirs(3, 20, seed=1, n_max_iter=200)
@@ -267,6 +284,11 @@ def test_wide_mlp_config_matches_fp32_reference():
     np.testing.assert_allclose(Fe[..., 0], outs[0][1][..., 0], rtol=1e-5, atol=1e-7)
     np.testing.assert_allclose(Fe[..., 1], outs[0][1][..., 1], rtol=1e-12, atol=1e-15)
     np.testing.assert_array_equal(Fe[..., 2], outs[0][1][..., 2])
+    fixed = _fixed_features(p, eng.stored_genes())
+    for b in range(X.shape[0]):
+        ref = do.evaluate_device_order(probs[b], outs[0][0][b], codes, fixed=fixed,
+                                       kernel="mlpw32")
+        np.testing.assert_array_equal(outs[0][1][b], ref)
 
 
 # ------------------------------------------------------------------ bf16 perf mode
@@ -298,8 +320,8 @@ def _bf16_forward(x_ml, mut, W, bs):
 
 @pytest.mark.parametrize("wide", [False, True])
 def test_bf16_mode_classifier(wide):
-    """mv_set_mlp_precision(bf16): k_mlp2 (shipped botnet net) / k_mlp (configs[4] wide net)
-    on bf16 MFMA.  f1 matches the numpy restatement of the bf16 arithmetic (accumulation order
+    """mv_set_mlp_precision(bf16): k_mlp2 (shipped botnet net) / k_mlpw (configs[4] wide net;
+    with biases and at its other widths: tests/test_gpu_classifier_routes.py) on bf16 MFMA.  f1 matches the numpy restatement of the bf16 arithmetic (accumulation order
     aside: 2e-3 absolute), stays close to the fp32 parity value (0.05 absolute on these rows),
     f2/f3 are unchanged, and an attack in bf16 mode reports the bf16 f1 of its final genes."""
     from moeva2_amd.attacks.moeva2.classifier import Classifier, DenseMLPModel
