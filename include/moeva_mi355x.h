@@ -255,6 +255,17 @@ int mv_attack_front(mv_engine* e, uint8_t* front, int32_t* offsets, double* X, d
 /* History rows per state = P + (n_gen-1)*O, width 3 (reduced) or 3+C (full): hist [B][rows][w]
  * a device buffer or page-locked host memory (hipHostMalloc / registered: one DMA). */
 int mv_attack_history(mv_engine* e, double* hist, void* stream);
+/* What the last mv_attack_run's survival calls took over from the call before them (engine
+ * extension; results do not depend on it).  A state's survivors keep their objectives, so
+ * when all of them came from front 0 the next call skips the dominance work among them, and
+ * when the ideal point and the nadir keep their bits the next call takes the survivors'
+ * niche and distance from their pool slots instead of sweeping the reference directions.
+ * Host arrays [B]: dom_skipped the calls that skipped dominance work items (the population
+ * holds a whole 64-row block), assoc_reused the calls that reused the association.  Both
+ * are zero before the first attack on the bound states, and stay zero with MV_SURV_CARRY=0
+ * in the environment when the engine was created; mv_survive (no engine) carries nothing.
+ * Synchronises the device. */
+int mv_get_survival_carry(mv_engine* e, int32_t* dom_skipped, int32_t* assoc_reused);
 /* The attack's gene layout for the bound states (engine extension; no reference
  * counterpart).  mv_set_states finds the genes no attack on those states can change --
  * integer genes whose bounds are equal and whose initial value is that bound in every state

@@ -157,6 +157,14 @@ struct mv_engine {
   double* plan_mu = nullptr;
   double *ideal = nullptr, *worst = nullptr, *extreme = nullptr;
   int* has_ext = nullptr;
+  // what survivors carry between survival calls (SurvArgs.carry_flag ...); MV_SURV_CARRY=0,
+  // read when the engine is created, makes every call recompute everything (A/B)
+  bool surv_carry = true;
+  int* carry_flag = nullptr;
+  unsigned long long* carry_bits = nullptr;
+  int* slot_niche = nullptr;
+  double* slot_dist = nullptr;
+  int* carry_cnt = nullptr;
   double* ref = nullptr;
   std::vector<double> ref_host;  // the reference points currently in e->ref
   double* hist = nullptr;
@@ -528,6 +536,7 @@ int mv_engine_create(int32_t device, const mv_problem_desc* pd, const mv_model_d
   HIPCHK(hipSetDevice(device));
   mv_engine* e = new mv_engine();
   e->device = device;
+  if (const char* c = std::getenv("MV_SURV_CARRY")) e->surv_carry = c[0] != '0';
   HostProblem& h = e->hp;
   h.D = D;
   h.V = V;
@@ -978,6 +987,11 @@ int mv_attack_run(mv_engine* e, const mv_attack_params* prm, void* stream_) {
     A(&e->worst, (size_t)B * 3);
     A(&e->extreme, (size_t)B * 9);
     A(&e->has_ext, (size_t)B);
+    A(&e->carry_flag, (size_t)B * 2);
+    A(&e->carry_bits, (size_t)B * 6);
+    A(&e->slot_niche, (size_t)B * S);
+    A(&e->slot_dist, (size_t)B * S);
+    A(&e->carry_cnt, (size_t)B * 2);
     A(&e->ref, (size_t)R * 3);
     if (prm->history) A(&e->hist, (size_t)B * hist_rows * hist_w);
     if (err != hipSuccess)
@@ -1008,6 +1022,9 @@ int mv_attack_run(mv_engine* e, const mv_attack_params* prm, void* stream_) {
   hipLaunchKernelGGL(k_fill_d, dim3(64), dim3(256), 0, stream, e->worst, (size_t)B * 3,
                      (double)-INFINITY);
   hipLaunchKernelGGL(k_fill_i, dim3(64), dim3(256), 0, stream, e->has_ext, (size_t)B, 0);
+  // nothing is carried into an attack's first survival; its counters start at zero
+  hipLaunchKernelGGL(k_fill_i, dim3(64), dim3(256), 0, stream, e->carry_flag, (size_t)B * 2, 0);
+  hipLaunchKernelGGL(k_fill_i, dim3(64), dim3(256), 0, stream, e->carry_cnt, (size_t)B * 2, 0);
   HIPCHK(hipGetLastError());
   HIPCHK(launch_init_pool(B, P, O, V, S, e->ag0(), e->pool, e->pop_slot, e->free_slot, stream));
   HIPCHK(e->ensure_xml((size_t)B * (P > O ? P : O)));
@@ -1074,6 +1091,13 @@ int mv_attack_run(mv_engine* e, const mv_attack_params* prm, void* stream_) {
     s.worst += b0 * 3;
     s.extreme += b0 * 9;
     s.has_extreme += b0;
+    if (s.carry_flag) {
+      s.carry_flag += b0 * 2;
+      s.carry_bits += b0 * 6;
+      s.slot_niche += b0 * S;
+      s.slot_dist += b0 * S;
+      s.carry_cnt += b0 * 2;
+    }
     s.key0 += (uint32_t)b0;
     if (s.parents_out) s.parents_out += b0 * O;
     if (s.phase) s.phase += b0 * 32;
@@ -1116,6 +1140,13 @@ int mv_attack_run(mv_engine* e, const mv_attack_params* prm, void* stream_) {
   sa.worst = e->worst;
   sa.extreme = e->extreme;
   sa.has_extreme = e->has_ext;
+  if (e->surv_carry) {
+    sa.carry_flag = e->carry_flag;
+    sa.carry_bits = e->carry_bits;
+    sa.slot_niche = e->slot_niche;
+    sa.slot_dist = e->slot_dist;
+    sa.carry_cnt = e->carry_cnt;
+  }
   sa.O_next = O;
   sa.dom_g = e->dom_g;
   sa.dom_stride = e->dom_stride;
@@ -1799,6 +1830,24 @@ int mv_set_gene_layout(mv_engine* e, const int32_t* stored, int32_t V) {
     if (stored[g]) keep.push_back(g);
   if (keep.empty()) return fail(MV_ERR_ARG, "mv_set_gene_layout: no stored gene");
   e->layout_req = keep;
+  return MV_OK;
+}
+
+int mv_get_survival_carry(mv_engine* e, int32_t* dom_skipped, int32_t* assoc_reused) {
+  if (!e || !dom_skipped || !assoc_reused) return fail(MV_ERR_ARG, "null argument");
+  if (e->B <= 0) return fail(MV_ERR_STATE, "no states bound (mv_set_states)");
+  if (!e->attack_ready) {  // no attack on these states yet
+    for (int b = 0; b < e->B; ++b) dom_skipped[b] = assoc_reused[b] = 0;
+    return MV_OK;
+  }
+  HIPCHK(hipSetDevice(e->device));
+  std::vector<int> c((size_t)e->B * 2);
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(c.data(), e->carry_cnt, c.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (int b = 0; b < e->B; ++b) {
+    dom_skipped[b] = c[(size_t)b * 2];
+    assoc_reused[b] = c[(size_t)b * 2 + 1];
+  }
   return MV_OK;
 }
 

@@ -251,6 +251,20 @@ struct SurvArgs {
   double cx_prob;
   int cx_sbx;               // SBX: the subsets' mating-level draws only
   int wide;                 // N <= SURV_NLDS: SURV_T_MID threads per state instead of SURV_T
+  // What a state's survivors carry to its next survival call (slot mode only; all NULL: every
+  // call recomputes everything -- dense mode, MV_SURV_CARRY=0).  The merged rows below P are
+  // the previous call's survivors and their F does not change, so
+  //   carry_flag[b][0]: every survivor came from front 0 -> no pair of them dominates: the
+  //                     dominance work items that lie wholly below P are skipped;
+  //   carry_flag[b][1]: slot_niche / slot_dist / carry_bits hold the previous call's values;
+  //                     when this call's ideal and nadir have the bits of carry_bits, the unit
+  //                     directions are the same and a survivor's (niche, dist) is taken from
+  //                     its slot instead of the sweep over the directions.
+  int* carry_flag;                  // [B][2]
+  unsigned long long* carry_bits;   // [B][6] bit patterns of ideal(3), nadir(3)
+  int* slot_niche;                  // [B][S]
+  double* slot_dist;                // [B][S]
+  int* carry_cnt;                   // [B][2] calls that skipped dominance items / reused niches
 };
 
 // Stand-alone classifier forward (Classifier.predict_proba) -------------------------------

@@ -589,6 +589,15 @@ __device__ __forceinline__ void survive_state(const SurvArgs& a, const int b, co
   const double pre_ideal = tid < 3 ? a.ideal[(size_t)b * 3 + tid] : 0.0;
   const double pre_worst = tid < 3 ? a.worst[(size_t)b * 3 + tid] : 0.0;
   const bool slot_mode = a.pop_slot != nullptr;
+  // carried from the previous call (SurvArgs.carry_flag; uniform): the rows below P are
+  // mutually non-dominated / their (niche, dist) are in their slots
+  const bool carry = slot_mode && a.carry_flag != nullptr;
+  const int nd_in = carry ? a.carry_flag[(size_t)b * 2] : 0;
+  const int av_in = carry ? a.carry_flag[(size_t)b * 2 + 1] : 0;
+  unsigned long long* pbits = (unsigned long long*)(L.scal + 12);  // 6: carried ideal, nadir
+  // whole 64-row blocks / (LDS bitsets) whole 16-row quarters of known non-dominated rows
+  const int nbi = nd_in ? a.P >> 6 : 0;
+  const int njq = NWMAX * 64 > SURV_NLDS ? 4 * nbi : (nbi ? a.P >> 4 : 0);
 #define PHASE(k) \
   if (MV_CLOCKS && a.phase && tid == 0) a.phase[(size_t)b * 32 + (k)] = clock64();
   PHASE(0)
@@ -611,6 +620,30 @@ __device__ __forceinline__ void survive_state(const SurvArgs& a, const int b, co
     L.slot[m] = s;
     L.front_of[m] = -1;
     L.sel[m] = 0;
+    if (av_in && m < a.P) {  // the survivor's carried (niche, dist), staged by merged index
+      L.surv[m] = a.slot_niche[(size_t)b * a.S + s];  // in arrays that are idle until the
+      L.sortk[m] =                                     // association / the survivor selection
+          (unsigned long long)__double_as_longlong(a.slot_dist[(size_t)b * a.S + s]);
+    }
+  }
+  if (av_in && tid < 6) pbits[tid] = a.carry_bits[(size_t)b * 6 + tid];
+  if (nbi > 0) {
+    // the bits the skipped dominance items (below) would have written, all zero: dominator i,
+    // dominated j with min(i, j) inside the whole blocks and max(i, j) inside the whole
+    // quarters -- words q < nbi of the rows below 16 njq, and the 16-bit pieces between the
+    // whole blocks and the last whole quarter of the rows below 64 nbi
+    const int PB = nbi * 64, PQ = njq * 16;
+    for (int t = tid; t < nbi * PQ; t += T) {
+      const int q = t / PQ, j = t - q * PQ;
+      L.dom[(size_t)q * N + j] = 0ull;
+    }
+    if (NWMAX * 64 <= SURV_NLDS) {
+      unsigned short* dom16 = (unsigned short*)L.dom;
+      for (int t = tid; t < (njq - 4 * nbi) * PB; t += T) {
+        const int c = 4 * nbi + t / PB, j = t % PB;
+        dom16[((size_t)(c >> 2) * N + j) * 4 + (c & 3)] = (unsigned short)0;
+      }
+    }
   }
   for (int m = N + tid; m < NW * 64; m += T) {  // padding rows: compare false both ways
     L.F[m * 3 + 0] = __builtin_nan("");
@@ -690,18 +723,21 @@ __device__ __forceinline__ void survive_state(const SurvArgs& a, const int b, co
     // the word-major layout (dom[q N + j]): lane u's ballot word qi of dom[j0 + u] and lane
     // l's 64-bit word qj of dom[i] are 512 contiguous bytes each (the quarter items' 2-byte
     // stores to rows 128 B apart cost 28.8 GB of HBM traffic per configs[3] launch)
-    const int n_b = NW * (NW + 1) / 2;
+    // Only the live pairs are numbered: with nbi whole blocks of known non-dominated rows
+    // (above) block row qi < nbi starts at block nbi instead of qi.
+    const int n_b = NW * (NW + 1) / 2 - nbi * (nbi + 1) / 2;
     for (;;) {
       int t = 0;
       if (lane == 0) t = atomicAdd(&L.iscal[14], 1);
       t = __builtin_amdgcn_readfirstlane(t);  // lane 0 is the first active lane
       if (t >= n_b) break;
-      int qi = 0, rem = t;
-      while (rem >= NW - qi) {
-        rem -= NW - qi;
+      int qi = 0, rem = t, c0 = nbi;
+      while (rem >= NW - c0) {
+        rem -= NW - c0;
         ++qi;
+        c0 = qi < nbi ? nbi : qi;
       }
-      const int qj = qi + rem;
+      const int qj = c0 + rem;
       const int i = qi * 64 + lane;
       const double fi0 = L.F[i * 3 + 0], fi1 = L.F[i * 3 + 1], fi2 = L.F[i * 3 + 2];
       const int j0 = qj * 64;
@@ -715,19 +751,23 @@ __device__ __forceinline__ void survive_state(const SurvArgs& a, const int b, co
     }
   } else {
     unsigned short* dom16 = (unsigned short*)L.dom;
-    const int n_q = NW * (NW + 1) * 2;  // block pairs x 4 quarters
+    // block pairs x 4 quarters; only the live items are numbered: block row qi takes the
+    // quarters c = 4 qj + qq from 4 qi on, or from njq on when qi < nbi (the quarters before
+    // njq hold known non-dominated rows, as block qi does: zero-filled above)
+    const int n_q = NW * (NW + 1) * 2 - (nbi * njq - 2 * nbi * (nbi - 1));
     for (;;) {
       int t = 0;
       if (lane == 0) t = atomicAdd(&L.iscal[14], 1);
       t = __builtin_amdgcn_readfirstlane(t);  // lane 0 is the first active lane
       if (t >= n_q) break;
-      const int qq = t & 3;
-      int qi = 0, rem = t >> 2;
-      while (rem >= NW - qi) {
-        rem -= NW - qi;
+      int qi = 0, rem = t, c0 = njq;
+      while (rem >= 4 * NW - c0) {
+        rem -= 4 * NW - c0;
         ++qi;
+        c0 = qi < nbi ? njq : 4 * qi;
       }
-      const int qj = qi + rem;
+      const int qq = (c0 + rem) & 3;
+      const int qj = (c0 + rem) >> 2;
       const int i = qi * 64 + lane;
       const double fi0 = L.F[i * 3 + 0], fi1 = L.F[i * 3 + 1], fi2 = L.F[i * 3 + 2];
       const int j0 = qj * 64 + qq * 16;
@@ -987,6 +1027,18 @@ __device__ __forceinline__ void survive_state(const SurvArgs& a, const int b, co
     PHASE(26)
   }
   PHASE(4)
+  // The unit directions below depend on the reference points, mu, the ideal point and the
+  // nadir only: with the previous call's ideal and nadir (bit patterns, so NaN and -0 match
+  // themselves only) the survivors' carried (niche, dist) are what the sweep would give.
+  bool reuse = false;
+  if (av_in) {
+    int eq = 1;
+    for (int k = 0; k < 3; ++k) {
+      eq &= (unsigned long long)__double_as_longlong(ideal[k]) == pbits[k] ? 1 : 0;
+      eq &= (unsigned long long)__double_as_longlong(nadir[k]) == pbits[3 + k] ? 1 : 0;
+    }
+    reuse = __builtin_amdgcn_readfirstlane(eq) != 0;  // the same in every thread
+  }
 
   // ---- aspiration reference directions (normalised), R points + 3 extreme axes
   {
@@ -1021,7 +1073,10 @@ __device__ __forceinline__ void survive_state(const SurvArgs& a, const int b, co
       for (int k = 0; k < 3; ++k) L.U[r * 3 + k] = res[k] / nrm;
       L.Uf[r] = make_double4(L.U[r * 3], L.U[r * 3 + 1], L.U[r * 3 + 2], 0.0);
     }
-    if (tid == 0) L.iscal[15] = 0;
+    if (tid == 0) {
+      L.iscal[15] = 0;
+      L.iscal[13] = 0;  // ranked offspring to associate (reuse)
+    }
     __syncthreads();
   }
   PHASE(5)
@@ -1040,8 +1095,25 @@ __device__ __forceinline__ void survive_state(const SurvArgs& a, const int b, co
     // the sequential scan).
     const int nh = RN >> 1;  // directions per half (wave-uniform loop counts); an odd RN's
                              // last direction goes to the second half's chain 0
-    for (int v = tid; v < 2 * n_ranked; v += T) {
-      const int p = v >> 1, hf = v & 1;
+    // reuse: the ranked survivors (merged index below P) take the (niche, dist) staged at
+    // entry; the ranked offspring are listed (any order: each writes its own position) so the
+    // sweep's lane pairs stay dense in the first waves
+    int n_assoc = n_ranked;
+    if (reuse) {
+      for (int p = tid; p < n_ranked; p += T) {
+        const int m = L.I[p];
+        if (m < a.P) {
+          L.niche[p] = L.surv[m];
+          L.dist[p] = __longlong_as_double((long long)L.sortk[m]);
+        } else {
+          L.memb[atomicAdd(&L.iscal[13], 1)] = p;
+        }
+      }
+      __syncthreads();
+      n_assoc = L.iscal[13];
+    }
+    for (int v = tid; v < 2 * n_assoc; v += T) {
+      const int p = reuse ? L.memb[v >> 1] : v >> 1, hf = v & 1;
       const int jb = hf ? nh : 0;
       const bool odd = hf && (RN & 1);
       const int m = L.I[p];
@@ -1374,9 +1446,14 @@ __device__ __forceinline__ void survive_state(const SurvArgs& a, const int b, co
   for (int k = tid; k < N; k += T) L.memb[k] = 0;  // selected flags by merged index
   __syncthreads();
   for (int k = tid; k < n_out; k += T) {
-    const int m = L.I[L.surv[k]];
+    const int p = L.surv[k];
+    const int m = L.I[p];
     L.memb[m] = 1;
     L.sel[k] = L.slot[m];  // new population order -> slot (read by the tournament below)
+    if (carry) {  // the survivor's association, for the next call
+      a.slot_niche[(size_t)b * a.S + L.slot[m]] = L.niche[p];
+      a.slot_dist[(size_t)b * a.S + L.slot[m]] = L.dist[p];
+    }
     if (slot_mode)
       a.pop_slot_out[(size_t)b * a.n_survive + k] = L.slot[m];
     else
@@ -1403,6 +1480,18 @@ __device__ __forceinline__ void survive_state(const SurvArgs& a, const int b, co
     }
     for (int k = 0; k < 9; ++k) a.extreme[(size_t)b * 9 + k] = ext[k];
     a.has_extreme[b] = 1;
+    if (carry) {
+      // fronts are taken whole until the last one, so the survivors are all of front 0
+      // exactly when only front 0 was ranked
+      a.carry_flag[(size_t)b * 2] = nf == 1 && n_out == a.n_survive ? 1 : 0;
+      a.carry_flag[(size_t)b * 2 + 1] = 1;
+      for (int k = 0; k < 3; ++k) {
+        a.carry_bits[(size_t)b * 6 + k] = (unsigned long long)__double_as_longlong(ideal[k]);
+        a.carry_bits[(size_t)b * 6 + 3 + k] = (unsigned long long)__double_as_longlong(nadir[k]);
+      }
+      if (nbi > 0) a.carry_cnt[(size_t)b * 2] += 1;
+      if (reuse) a.carry_cnt[(size_t)b * 2 + 1] += 1;
+    }
   }
   __syncthreads();
   if (slot_mode && N > a.n_survive) {

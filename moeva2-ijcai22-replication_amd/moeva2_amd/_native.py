@@ -27,7 +27,7 @@ EXPORTED = [
     "mv_last_error", "mv_device_count", "mv_engine_create", "mv_engine_destroy",
     "mv_set_states", "mv_evaluate", "mv_decode", "mv_constraints", "mv_survive", "mv_select_parents",
     "mv_variation", "mv_attack_run", "mv_attack_population", "mv_attack_front",
-    "mv_attack_history",
+    "mv_attack_history", "mv_get_survival_carry",
     "mv_set_profiling", "mv_get_kernel_times", "mv_get_phase_times", "mv_get_row_kernel",
     "mv_get_mlp_kernel", "mv_set_attack_mode",
     "mv_set_crossover", "mv_set_mlp_precision",
@@ -122,6 +122,7 @@ def lib():
             "mv_attack_population": [vp, vp, vp, vp],
             "mv_attack_front": [vp, vp, vp, vp, vp, vp],
             "mv_attack_history": [vp, vp, vp],
+            "mv_get_survival_carry": [vp, _i32p, _i32p],
             "mv_set_profiling": [vp, C.c_int32],
             "mv_get_kernel_times": [vp, _f64p, _f64p, _f64p, _i32p],
             "mv_get_phase_times": [vp, _f64p, _i32p],
@@ -386,6 +387,16 @@ class Engine:
         else:
             p = _ptr(hist)
         check(lib().mv_attack_history(self._h, p, _stream(stream)))
+
+    def survival_carry(self):
+        """Per state, the survival calls of the last attack that skipped dominance work among
+        the survivors and that reused their association (mv_get_survival_carry): two int32
+        arrays (B,)."""
+        dom = np.zeros(self.B, np.int32)
+        assoc = np.zeros(self.B, np.int32)
+        check(lib().mv_get_survival_carry(self._h, dom.ctypes.data_as(_i32p),
+                                          assoc.ctypes.data_as(_i32p)))
+        return dom, assoc
 
     def set_profiling(self, on: bool):
         check(lib().mv_set_profiling(self._h, int(on)))
