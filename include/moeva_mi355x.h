@@ -58,7 +58,35 @@ enum {
   MV_OP_TF_RATIO_ALPHA_NEG = 13,  /* |x[a0] - (isnan(x[a1]/x[a2]) ? -1 : x[a1]/(x[a2]+k0))|  lcld:147-151 */
   MV_OP_TF_RATIO_ALPHA_ZERO = 14, /* isnan(x[a0]-x[a1]) ? 0 : x[a0]/(x[a1]+k0)   botnet:250-269 */
   MV_OP_TF_ABS_SUMDIFF_OFF = 15,  /* |sum(pool[a0:a1]) - sum(pool[a1:a2])| - k0  botnet:55-75 */
+  /* user-defined column (engine extension; no reference counterpart): a postfix expression
+   * over the row, interpreted on the device in fp64.  op_arg = (a0 offset of its first word in
+   * expr_code, a1 word count, a2 maximum stack depth, 0).  mv_engine_create simulates every
+   * such column and refuses a malformed one (MV_ERR_ARG), so the device only ever interprets
+   * checked code. */
+  MV_OP_EXPR = 16,
 };
+
+/* MV_OP_EXPR bytecode: int32 words, postfix, operands inline; a binary operator pops b, then
+ * a, and pushes a . b (the left operand was pushed first).  Semantics are numpy's on fp64. */
+enum {
+  MV_X_FEAT = 1,   /* X f      push x[f]                         0 <= f < D */
+  MV_X_CONST = 2,  /* K i      push expr_const[i]                0 <= i < n_expr_const */
+  MV_X_SUMF = 3,   /* SUMF o0 o1  push 0.0 + x[idx_pool[o0]] + ... + x[idx_pool[o1-1]], left to
+                      right; 0 <= o0 <= o1 <= n_pool */
+  MV_X_ADD = 4, MV_X_SUB = 5, MV_X_MUL = 6,
+  MV_X_DIV = 7,    /* IEEE: x/0 = +-inf or NaN */
+  MV_X_MIN = 8, MV_X_MAX = 9,  /* np.minimum / np.maximum: NaN propagates */
+  MV_X_MOD = 10,   /* np.mod: the result takes the divisor's sign */
+  MV_X_POW = 11,   /* pow(a, b), the pow of MV_OP_LCLD_INSTALL */
+  MV_X_LT = 12, MV_X_LE = 13, MV_X_GT = 14, MV_X_GE = 15, MV_X_EQ = 16, MV_X_NE = 17, /* 1.0/0.0 */
+  MV_X_AND = 18, MV_X_OR = 19, MV_X_XOR = 20,  /* on the truth values a != 0, b != 0 */
+  MV_X_NEG = 21, MV_X_ABS = 22, MV_X_FLOOR = 23,
+  MV_X_NOT = 24,   /* a == 0 */
+  MV_X_ISNAN = 25, MV_X_ISINF = 26,
+  MV_X_WHERE = 27, /* pops b, a, c; pushes c != 0 ? a : b */
+};
+/* Limits of one MV_OP_EXPR column. */
+enum { MV_EXPR_MAX_DEPTH = 8, MV_EXPR_MAX_WORDS = 256 };
 
 typedef struct mv_problem_desc {
   int32_t D;                  /* ML feature count */
@@ -81,6 +109,12 @@ typedef struct mv_problem_desc {
   double tol;                 /* constraints <= tol -> 0  (1e-3 in every reference class) */
   int32_t norm;               /* 2 = L2, 0 = Linf  (default_problem.py:80-91) */
   int32_t scale_objectives;   /* f2 MinMax scaling (utils.py:11-22) */
+  /* MV_OP_EXPR bytecode (appended: a zero-initialised struct describes a program without
+   * EXPR columns) */
+  int32_t n_expr_code;        /* code words of all EXPR columns */
+  const int32_t* expr_code;   /* host [n_expr_code] */
+  int32_t n_expr_const;       /* constants */
+  const double* expr_const;   /* host [n_expr_const] */
 } mv_problem_desc;
 
 typedef struct mv_model_desc {
@@ -215,7 +249,8 @@ typedef struct mv_attack_params {
  * survive}, no host round trip.  Asynchronous on `stream`.  Replaces Moeva2.generate's
  * per-state pymoo.minimize calls (moeva2.py:128-171, 194-205) for ALL bound states.
  * Schedule: per generation the row kernel (k_genc for wide IDENT rows such as botnet,
- * k_narrow for LCLD-shaped rows, else k_gen + k_cons), the classifier (k_mlp2 / k_mlpw /
+ * k_narrow for LCLD-shaped rows, else k_gen + k_cons; a program with MV_OP_EXPR columns
+ * always k_gen + k_consx), the classifier (k_mlp2 / k_mlpw /
  * k_mlp) and k_survive (survival + the next tournament), the states split into up to 4
  * groups, each chain on its own stream. */
 int mv_attack_run(mv_engine* e, const mv_attack_params* params, void* stream);

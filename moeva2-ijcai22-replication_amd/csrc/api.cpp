@@ -357,6 +357,8 @@ static int build_problem(const HostProblem& h, const HostModel* hm, const std::v
   p.full_ops = 0;
   for (int c = 0; c < C; ++c)
     if (h.op_code[c] >= MV_OP_LCLD_INSTALL && h.op_code[c] <= MV_OP_RATIO_MASKED) p.full_ops = 1;
+  for (int c = 0; c < C; ++c)  // an EXPR column: the interpreter instances (k_gen + k_consx)
+    if (h.op_code[c] == MV_OP_EXPR) p.full_ops = 2;
   p.ident = V == Dm;
   for (int c = 0; c < V && p.ident; ++c) p.ident = kind[c] != MV_GENE_OHE && feat[c] == mut[c];
   {  // k_vary problem blob: the LDS image of the tables (kernels.h vary_offsets)
@@ -493,6 +495,83 @@ static int build_problem(const HostProblem& h, const HostModel* hm, const std::v
   return MV_OK;
 }
 
+// MV_OP_EXPR columns: simulate every column's bytecode on the host -- known opcodes, operands
+// in range, no stack underflow, depth within the limit, exactly one value left, word count
+// within the limit -- so the device interpreter (rowops.h eval_expr) only ever runs checked
+// code.  On success the bytecode and its constants join the host problem's index pool after
+// the caller's n_pool entries (code words, then -- 8-byte aligned -- the constants' bits), and
+// each column's op_arg becomes (pool offset of its first word, word count, pool offset of
+// the constant table, depth): the kernels reach both through the pool tables they already
+// stage, and a program without EXPR columns keeps its tables to the byte.
+static int expr_check(const mv_problem_desc* pd) {
+  const int C = pd->C, D = pd->D, n_pool = pd->n_pool;
+  bool any = false;
+  for (int c = 0; c < C; ++c) any |= pd->op_code[c] == MV_OP_EXPR;
+  if (!any) return MV_OK;
+  const int nw = pd->n_expr_code, nk = pd->n_expr_const;
+  if (nw <= 0 || !pd->expr_code || nk < 0 || (nk > 0 && !pd->expr_const))
+    return fail(MV_ERR_ARG, "MV_OP_EXPR column without expr_code / expr_const");
+  auto bad = [&](int c, const char* what) {
+    return fail(MV_ERR_ARG, "MV_OP_EXPR column " + std::to_string(c) + ": " + what);
+  };
+  for (int c = 0; c < C; ++c) {
+    if (pd->op_code[c] != MV_OP_EXPR) continue;
+    const int off = pd->op_arg[(size_t)c * 4], n = pd->op_arg[(size_t)c * 4 + 1];
+    const int dmax = pd->op_arg[(size_t)c * 4 + 2];
+    if (n < 1) return bad(c, "empty expression");
+    if (n > MV_EXPR_MAX_WORDS) return bad(c, "more than MV_EXPR_MAX_WORDS code words");
+    if (off < 0 || off > nw - n) return bad(c, "code range outside expr_code");
+    if (dmax < 1 || dmax > MV_EXPR_MAX_DEPTH) return bad(c, "stack depth outside 1..MV_EXPR_MAX_DEPTH");
+    const int32_t* w = pd->expr_code + off;
+    int depth = 0, pc = 0;
+    while (pc < n) {
+      const int op = w[pc++];
+      int pops = 0, operands = 0;
+      if (op == MV_X_FEAT || op == MV_X_CONST) operands = 1;
+      else if (op == MV_X_SUMF) operands = 2;
+      else if (op >= MV_X_ADD && op <= MV_X_XOR) pops = 2;
+      else if (op >= MV_X_NEG && op <= MV_X_ISINF) pops = 1;
+      else if (op == MV_X_WHERE) pops = 3;
+      else return bad(c, "unknown opcode");
+      if (pc + operands > n) return bad(c, "operand past the end of the column");
+      if (op == MV_X_FEAT && (w[pc] < 0 || w[pc] >= D)) return bad(c, "feature index out of range");
+      if (op == MV_X_CONST && (w[pc] < 0 || w[pc] >= nk)) return bad(c, "constant index out of range");
+      if (op == MV_X_SUMF) {
+        const int o0 = w[pc], o1 = w[pc + 1];
+        if (o0 < 0 || o1 < o0 || o1 > n_pool) return bad(c, "pool range out of range");
+        for (int q = o0; q < o1; ++q)
+          if (pd->idx_pool[q] < 0 || pd->idx_pool[q] >= D) return bad(c, "pool feature out of range");
+      }
+      pc += operands;
+      if (depth < pops) return bad(c, "stack underflow");
+      depth += 1 - pops;
+      if (depth > dmax) return bad(c, "stack deeper than the column declares");
+    }
+    if (depth != 1) return bad(c, "the column does not end with exactly one value");
+  }
+  return MV_OK;
+}
+static void expr_append(const mv_problem_desc* pd, HostProblem& h) {
+  const int C = pd->C, nw = pd->n_expr_code, nk = pd->n_expr_const;
+  bool any = false;
+  for (int c = 0; c < C; ++c) any |= pd->op_code[c] == MV_OP_EXPR;
+  if (!any) return;
+  const int code_at = (int)h.pool.size();
+  h.pool.insert(h.pool.end(), pd->expr_code, pd->expr_code + nw);
+  if (h.pool.size() & 1) h.pool.push_back(0);
+  const int const_at = (int)h.pool.size();
+  h.pool.resize(h.pool.size() + (size_t)2 * nk);
+  if (nk) std::memcpy(h.pool.data() + const_at, pd->expr_const, (size_t)nk * 8);
+  h.n_pool = (int)h.pool.size();
+  for (int c = 0; c < C; ++c) {
+    if (h.op_code[c] != MV_OP_EXPR) continue;
+    int* ar = &h.op_arg[(size_t)c * 4];
+    ar[3] = ar[2];
+    ar[0] += code_at;
+    ar[2] = const_at;
+  }
+}
+
 extern "C" {
 
 const char* mv_last_error(void) { return g_err.c_str(); }
@@ -533,6 +612,7 @@ int mv_engine_create(int32_t device, const mv_problem_desc* pd, const mv_model_d
   }
   if (V > VARY_MAX_V || ((Dm + 15) & ~15) > VARY_MAX_V)
     return fail(MV_ERR_ARG, "genetic length / mutable features must be <= 1024");
+  if (const int rc = expr_check(pd)) return rc;
   HIPCHK(hipSetDevice(device));
   mv_engine* e = new mv_engine();
   e->device = device;
@@ -558,6 +638,7 @@ int mv_engine_create(int32_t device, const mv_problem_desc* pd, const mv_model_d
   h.op_arg.assign(pd->op_arg, pd->op_arg + (size_t)C * 4);
   h.op_k.assign(pd->op_karg, pd->op_karg + (size_t)C * 2);
   h.pool.assign(pd->idx_pool, pd->idx_pool + pd->n_pool);
+  expr_append(pd, h);
   h.mls.assign(D, 1.0);
   h.mlm.assign(D, 0.0);
   if (pd->ml_scale) std::memcpy(h.mls.data(), pd->ml_scale, D * sizeof(double));

@@ -673,7 +673,9 @@ __global__ __launch_bounds__(VARY_T) void k_gen(int slot, int gen, int hist_row0
 // evaluates its (register-packed) ops.
 // SLIM (k_genc, DProblem.slim): region S staged instead of region A, the lane ops' packed
 // words loaded straight from the problem blob (see kernels.h).
-template <bool FULL, bool IDENT, int NT, bool SLIM = false>
+// EXPR (k_consx): the program has MV_OP_EXPR columns, interpreted by their lanes (rowops.h
+// eval_expr); their words and constants are staged with region A's pool table.
+template <bool FULL, bool IDENT, int NT, bool SLIM = false, bool EXPR = false>
 __device__ __forceinline__ void cons_rows(const RowsArgs& a, int hist_row0, int rows_wg,
                                           unsigned char* smem, bool have_dst = false,
                                           int dst_pre = 0) {
@@ -778,7 +780,7 @@ __device__ __forceinline__ void cons_rows(const RowsArgs& a, int hist_row0, int 
 #pragma unroll
     for (int k = 0; k < OPS_REG; ++k) {
       const int c = lane + 64 * k;
-      opw[k] = (k < kops && c < tab.n_lane) ? pack_op(tab, c) : 0u;
+      opw[k] = (k < kops && c < tab.n_lane) ? pack_op<EXPR>(tab, c) : 0u;
     }
   }
   auto do_row = [&](int k, const double* x) {
@@ -804,7 +806,7 @@ __device__ __forceinline__ void cons_rows(const RowsArgs& a, int hist_row0, int 
     if constexpr (SLIM)
       f3 = constraints_slim(tab, so, srow, lane, grow, hc);
     else
-      f3 = constraints_regs<FULL>(tab, opw, kops, (const double*)xrow, lane, grow, hc);
+      f3 = constraints_regs<FULL, EXPR>(tab, opw, kops, (const double*)xrow, lane, grow, hc);
     // The row's destination is read from lane k HERE, with every lane active: a readlane
     // of a lane that is inactive at that point returns an undefined value.  (Round 3 read
     // it inside the lane-0 branch below.  Whenever the compiler spilled dst_v, its reload
@@ -836,6 +838,15 @@ template <bool FULL, bool IDENT, int NT>
 __global__ __launch_bounds__(CONS_T) void k_cons(int slot, int hist_row0, int rows_wg) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   cons_rows<FULL, IDENT, NT>(c_rows[slot], hist_row0, rows_wg, smem);
+}
+
+// k_consx: k_cons for a program with MV_OP_EXPR columns (every dedicated op stays available:
+// the two kinds mix in one program).  A kernel of its own, so a program without such a
+// column runs exactly the k_cons instances it always did.
+template <bool IDENT, int NT>
+__global__ __launch_bounds__(CONS_T) void k_consx(int slot, int hist_row0, int rows_wg) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  cons_rows<true, IDENT, NT, false, true>(c_rows[slot], hist_row0, rows_wg, smem);
 }
 
 // k_genc: k_gen and k_cons as two phases of ONE launch over the same row chunks (each wave
@@ -2428,10 +2439,9 @@ __global__ __launch_bounds__(EVAL_T) void k_predict(MlpArgs a) {
 }
 
 // Constraints only (Constraints.evaluate numpy path): one wave per ML-space row.
-template <bool FULL>
-__global__ __launch_bounds__(256) void k_constraints(int slot, int n,
-                                                     const double* x, double* G) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+template <bool FULL, bool EXPR = false>
+__device__ __forceinline__ void constraints_only(int slot, int n, const double* x, double* G,
+                                                 unsigned char* smem) {
   const DProblem& p = c_rows[slot].p;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = blockIdx.x * 4 + wave;
@@ -2439,7 +2449,19 @@ __global__ __launch_bounds__(256) void k_constraints(int slot, int n,
   double* xrow = (double*)smem + (size_t)wave * p.D;
   for (int f = lane; f < p.D; f += 64) xrow[f] = x[(size_t)r * p.D + f];
   wave_sync();
-  constraints_row<FULL>(global_tab(p), xrow, lane, G + (size_t)r * p.C, nullptr, false);
+  constraints_row<FULL, EXPR>(global_tab(p), xrow, lane, G + (size_t)r * p.C, nullptr, false);
+}
+template <bool FULL>
+__global__ __launch_bounds__(256) void k_constraints(int slot, int n,
+                                                     const double* x, double* G) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constraints_only<FULL>(slot, n, x, G, smem);
+}
+// ... of a program with MV_OP_EXPR columns (the bytecode is read from the global pool table)
+__global__ __launch_bounds__(256) void k_constraintsx(int slot, int n, const double* x,
+                                                      double* G) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constraints_only<true, true>(slot, n, x, G, smem);
 }
 
 // FeatureEncoder.genetic_to_ml (feature_encoder.py:91-130) for host plugins: genes
@@ -2572,7 +2594,8 @@ static void configure_lds_once() {
                        (const void*)k_mlp<4, false>, (const void*)k_mlp<8, false>,
                        (const void*)k_mlp<1, true>,  (const void*)k_mlp<2, true>,
                        (const void*)k_mlp<4, true>,  (const void*)k_mlp<8, true>,
-                       (const void*)k_constraints<false>, (const void*)k_constraints<true>};
+                       (const void*)k_constraints<false>, (const void*)k_constraints<true>,
+                       (const void*)k_constraintsx};
   for (const void* f : fns)
     (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
   (void)hipGetLastError();
@@ -2662,6 +2685,17 @@ static hipError_t gen_go(dim3 grid, size_t lds, hipStream_t s, int slot, int gen
   return hipGetLastError();
 }
 
+template <bool IDENT, int NT>
+static hipError_t consx_go(dim3 grid, size_t lds, hipStream_t s, int slot, int h0, int rw) {
+  static bool configured = false;
+  if (!configured) {
+    allow_lds(k_consx<IDENT, NT>);
+    configured = true;
+  }
+  MV_LAUNCH((k_consx<IDENT, NT>), grid, dim3(CONS_T), lds, s, slot, h0, rw);
+  return hipGetLastError();
+}
+
 template <bool FULL, bool IDENT, int NT>
 static hipError_t cons_go(dim3 grid, size_t lds, hipStream_t s, int slot, int h0, int rw) {
   static bool configured = false;
@@ -2679,7 +2713,8 @@ static hipError_t cons_go(dim3 grid, size_t lds, hipStream_t s, int slot, int h0
 static bool use_narrow(const RowsArgs& a) {
   const char* s = std::getenv("MV_NARROW");  // read per launch: tests flip it in-process
   return !(s && s[0] == '0') && a.do_eval && narrow_ok(a.p) && !(a.mode == 1 && a.cx_kind == 1) &&
-         !a.p.compact;  // the compact layout runs on the wave-per-row kernels only
+         !a.p.compact &&      // the compact layout runs on the wave-per-row kernels only
+         a.p.full_ops != 2;   // and so do MV_OP_EXPR columns (k_gen + k_consx)
 }
 
 template <int NV, bool FULL>
@@ -2816,6 +2851,22 @@ hipError_t launch_cons(const RowsArgs& a, int slot, int hist_row0, hipStream_t s
   const dim3 grid(B * ((a.n + rw - 1) / rw));
   const int nt = vary_nt(a.p);
   const size_t lds = cons_lds_total(vary_offsets(a.p));
+  if (a.p.full_ops == 2) {  // MV_OP_EXPR columns: the interpreter instances
+#define CONSX(I, N) return consx_go<I, N>(grid, lds, stream, slot, hist_row0, rw)
+    if (a.p.ident) {
+      if (nt == 1) CONSX(true, 1);
+      if (nt == 2) CONSX(true, 2);
+      if (nt == 4) CONSX(true, 4);
+      if (nt == 8) CONSX(true, 8);
+      CONSX(true, 16);
+    }
+    if (nt == 1) CONSX(false, 1);
+    if (nt == 2) CONSX(false, 2);
+    if (nt == 4) CONSX(false, 4);
+    if (nt == 8) CONSX(false, 8);
+    CONSX(false, 16);
+#undef CONSX
+  }
 #define CONS(F, I, N) return cons_go<F, I, N>(grid, lds, stream, slot, hist_row0, rw)
   if (a.p.full_ops) {  // LCLD programs: one-hot genes, few genes
     if (nt == 1) CONS(true, false, 1);
@@ -3081,7 +3132,9 @@ hipError_t launch_constraints(const DProblem& hp, int slot, int n, const double*
   configure_lds_once();
   const size_t lds = (size_t)4 * hp.D * sizeof(double);
   const dim3 grid((n + 3) / 4);
-  if (hp.full_ops)
+  if (hp.full_ops == 2)
+    MV_LAUNCH(k_constraintsx, grid, dim3(256), lds, stream, slot, n, x, G);
+  else if (hp.full_ops)
     MV_LAUNCH(k_constraints<true>, grid, dim3(256), lds, stream, slot, n, x, G);
   else
     MV_LAUNCH(k_constraints<false>, grid, dim3(256), lds, stream, slot, n, x, G);

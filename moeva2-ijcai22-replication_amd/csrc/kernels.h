@@ -44,7 +44,8 @@ __host__ __device__ inline size_t mlp_lds_bytes(int Dm4, int hmax, int Klast, in
 
 // Problem and per-state blobs: HBM images of LDS regions, each region 1-KiB aligned so a
 // workgroup stages the regions it needs with 16-B-per-lane global_load_lds copies.
-//   problem blob  A: constraint program (opa, opk, opc, ocol, pool)       -> k_cons
+//   problem blob  A: constraint program (opa, opk, opc, ocol, pool; the pool
+//                    table ends with the MV_OP_EXPR bytecode and constants) -> k_cons
 //                 B: mutation gap table, gene table, mutable features,
 //                    one-hot group offsets / features, cmap [Vr] (gene -> stored gene or
 //                    -1, fixed) and fidx [V] (stored gene -> gene)        -> k_gen

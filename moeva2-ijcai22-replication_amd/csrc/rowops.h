@@ -58,14 +58,85 @@ __device__ __forceinline__ OpTab global_tab(const DProblem& p) {
   return t;
 }
 
-// One constraint column on the ML row x (LDS).  FULL adds the LCLD financial identities;
+// An MV_OP_EXPR column (include/moeva_mi355x.h MV_X_*): the lane interprets the column's
+// postfix words, read from the pool table at ar.x .. ar.x + ar.y (constants: the doubles at
+// pool word ar.z); mv_engine_create has simulated them, so every operand is in range and the
+// stack never leaves its MV_EXPR_MAX_DEPTH = 8 slots.  The operand stack is eight named
+// registers that shift on push and pop -- s0 is the top -- so no slot is ever indexed by a
+// run-time value (an indexed array would live in scratch memory).  The lanes of a wave run
+// different columns: the wave serialises over the distinct opcodes of a step.
+template <class XR>
+__device__ __forceinline__ double eval_expr(const OpTab& t, const int4 ar, const XR& x) {
+  const int* w = t.pool + ar.x;
+  const int* const wend = w + ar.y;
+  const double* kc = (const double*)(t.pool + ar.z);
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0, s6 = 0.0, s7 = 0.0;
+  while (w < wend) {
+    const int op = *w++;
+    if (op <= 3) {  // X f, K i, SUMF o0 o1: push
+      const int a = *w++;
+      double v;
+      if (op == 1) {
+        v = x[a];
+      } else if (op == 2) {
+        v = kc[a];
+      } else {
+        const int o1 = *w++;
+        v = 0.0;
+        for (int q = a; q < o1; ++q) v += x[t.pool[q]];
+      }
+      s7 = s6, s6 = s5, s5 = s4, s4 = s3, s3 = s2, s2 = s1, s1 = s0, s0 = v;
+    } else if (op <= 20) {  // binary: a . b with b on top
+      const double a = s1, b = s0;
+      double r;
+      switch (op) {
+        case 4: r = a + b; break;
+        case 5: r = a - b; break;
+        case 6: r = a * b; break;
+        case 7: r = a / b; break;
+        case 8: r = (a < b || a != a) ? a : b; break;  // np.minimum: NaN propagates
+        case 9: r = (a > b || a != a) ? a : b; break;  // np.maximum
+        case 10: r = py_mod(a, b); break;
+        case 11: r = pow(a, b); break;
+        case 12: r = a < b ? 1.0 : 0.0; break;
+        case 13: r = a <= b ? 1.0 : 0.0; break;
+        case 14: r = a > b ? 1.0 : 0.0; break;
+        case 15: r = a >= b ? 1.0 : 0.0; break;
+        case 16: r = a == b ? 1.0 : 0.0; break;
+        case 17: r = a != b ? 1.0 : 0.0; break;
+        case 18: r = (a != 0.0) && (b != 0.0) ? 1.0 : 0.0; break;
+        case 19: r = (a != 0.0) || (b != 0.0) ? 1.0 : 0.0; break;
+        default: r = (a != 0.0) != (b != 0.0) ? 1.0 : 0.0; break;  // 20 XOR
+      }
+      s0 = r, s1 = s2, s2 = s3, s3 = s4, s4 = s5, s5 = s6, s6 = s7;
+    } else if (op <= 26) {  // unary
+      const double a = s0;
+      switch (op) {
+        case 21: s0 = -a; break;
+        case 22: s0 = fabs(a); break;
+        case 23: s0 = floor(a); break;
+        case 24: s0 = a == 0.0 ? 1.0 : 0.0; break;
+        case 25: s0 = a != a ? 1.0 : 0.0; break;
+        default: s0 = fabs(a) == __builtin_inf() ? 1.0 : 0.0; break;  // 26 ISINF
+      }
+    } else {  // 27 WHERE: c != 0 ? a : b
+      s0 = s2 != 0.0 ? s1 : s0;
+      s1 = s3, s2 = s4, s3 = s5, s4 = s6, s5 = s7;
+    }
+  }
+  return s0;
+}
+
+// One constraint column on the ML row x (LDS).  FULL adds the LCLD financial identities,
+// EXPR the user-defined columns (eval_expr);
 // ABS_SUMDIFF columns are evaluated wave-parallel (sumdiff_wave) by the caller.
 // XR: the row accessor -- a pointer to the LDS row, or any type with operator[](int) (the
 // narrow-row kernel's lane-strided row, narrow.h).
-template <bool FULL, class XR>
+template <bool FULL, bool EXPR = false, class XR>
 __device__ __forceinline__ double eval_op(const OpTab& t, int c, const XR& x) {
   const int code = t.code[c];
   const int4 ar = t.arg[c];
+  if (EXPR && code == 16) return eval_expr(t, ar, x);  // MV_OP_EXPR
   switch (code) {
     case 1:  // MV_OP_DIFF (botnet_constraints.py:283-285)
       return x[ar.x] - x[ar.y];
@@ -142,13 +213,13 @@ __device__ __forceinline__ double sumdiff_wave(const OpTab& t, int c, const XR& 
 
 // Constraint row -> G columns (+ history columns); returns the wave-uniform f3 = sum(G).
 // Values <= tol -> 0 (Constraints.evaluate); with clamp, G * (G > 0) (default_problem.py:93-97).
-template <bool FULL>
+template <bool FULL, bool EXPR = false>
 __device__ __forceinline__ double constraints_row(const OpTab& t, const double* xrow, int lane,
                                                   double* grow, double* hcols,
                                                   bool clamp_positive) {
   double acc3 = 0.0;
   for (int c = lane; c < t.n_lane; c += 64) {
-    double v = eval_op<FULL>(t, c, xrow);
+    double v = eval_op<FULL, EXPR>(t, c, xrow);
     if (v <= t.tol) v = 0.0;
     const double g = clamp_positive ? v * (v > 0.0 ? 1.0 : 0.0) : v;
     if (grow) grow[t.col[c]] = g;
@@ -174,13 +245,17 @@ __device__ __forceinline__ double constraints_row(const OpTab& t, const double* 
 // evaluated inline; other codes, and ops beyond OPS_REG per lane, go through eval_op.
 constexpr int OPS_REG = 6;
 
+// EXPR: an MV_OP_EXPR column packs to 0 -- its args are no features, and code 0 sends it to
+// eval_op.
+template <bool EXPR = false>
 __device__ __forceinline__ unsigned pack_op(const OpTab& t, int c) {
   const int4 ar = t.arg[c];
+  if (EXPR && t.code[c] == 16) return 0u;
   return (unsigned)t.code[c] | ((unsigned)ar.x << 4) | ((unsigned)ar.y << 18);
 }
 
 // (The slim program has its own straight-line form, constraints_slim below.)
-template <bool FULL, class XR>
+template <bool FULL, bool EXPR = false, class XR>
 __device__ __forceinline__ double constraints_regs(const OpTab& t, const unsigned* opw, int kops,
                                                    const XR& xrow, int lane, double* grow,
                                                    double* hcols) {
@@ -204,7 +279,7 @@ __device__ __forceinline__ double constraints_regs(const OpTab& t, const unsigne
       else if (code == 2)
         v = (vb[k] != 0.0 ? va[k] / vb[k] : 0.0) - t.k[c].x;
       else
-        v = eval_op<FULL>(t, c, xrow);
+        v = eval_op<FULL, EXPR>(t, c, xrow);
       if (v <= t.tol) v = 0.0;
       const double g = v * (v > 0.0 ? 1.0 : 0.0);
       const int col = MV_IDX(t.col[c], t.C, CK_CONS_COL);
@@ -214,7 +289,7 @@ __device__ __forceinline__ double constraints_regs(const OpTab& t, const unsigne
     }
   }
   for (int c = lane + 64 * OPS_REG; c < t.n_lane; c += 64) {
-    double v = eval_op<FULL>(t, c, xrow);
+    double v = eval_op<FULL, EXPR>(t, c, xrow);
     if (v <= t.tol) v = 0.0;
     const double g = v * (v > 0.0 ? 1.0 : 0.0);
     if (grow) grow[t.col[c]] = g;

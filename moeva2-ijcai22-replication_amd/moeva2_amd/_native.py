@@ -21,7 +21,9 @@ OP = dict(DIFF=1, RATIO_SAFE=2, ABS_SUMDIFF=3, LCLD_INSTALL=4, LCLD_TERM=5, ABS_
           MONTHDIFF=7, RATIO_MASKED=8, XOR_AUG=9,
           # tensor-path ops (C-PGD; mv_pgd_* only)
           TF_INSTALL_MIN=10, TF_HINGE_DIFF=11, TF_TERM_MIN=12, TF_RATIO_ALPHA_NEG=13,
-          TF_RATIO_ALPHA_ZERO=14, TF_ABS_SUMDIFF_OFF=15)
+          TF_RATIO_ALPHA_ZERO=14, TF_ABS_SUMDIFF_OFF=15,
+          # user-defined expression column (attacks/moeva2/expr.py bytecode)
+          EXPR=16)
 
 EXPORTED = [
     "mv_last_error", "mv_device_count", "mv_engine_create", "mv_engine_destroy",
@@ -51,6 +53,8 @@ class ProblemDesc(C.Structure):
         ("ml_scale", _f64p), ("ml_min", _f64p), ("op_code", _i32p), ("op_arg", _i32p),
         ("op_karg", _f64p), ("n_pool", C.c_int32), ("idx_pool", _i32p), ("tol", C.c_double),
         ("norm", C.c_int32), ("scale_objectives", C.c_int32),
+        ("n_expr_code", C.c_int32), ("expr_code", _i32p),
+        ("n_expr_const", C.c_int32), ("expr_const", _f64p),
     ]
 
 
@@ -253,6 +257,8 @@ class DeviceProgram:
     op_karg: np.ndarray  # (C,2)
     idx_pool: np.ndarray
     tol: float = 1e-3
+    expr_code: Optional[np.ndarray] = None  # int32 bytecode of the MV_OP_EXPR columns
+    expr_const: Optional[np.ndarray] = None  # fp64 constants of that bytecode
 
     @property
     def V(self):
@@ -298,6 +304,12 @@ class Engine:
         pd.op_karg = P(prog.op_karg, np.float64, C.c_double)
         pd.n_pool = int(prog.idx_pool.shape[0])
         pd.idx_pool = P(prog.idx_pool if prog.idx_pool.size else np.zeros(1), np.int32, C.c_int32)
+        xc = np.zeros(0, np.int32) if prog.expr_code is None else prog.expr_code
+        xk = np.zeros(0) if prog.expr_const is None else prog.expr_const
+        pd.n_expr_code = int(xc.shape[0])
+        pd.expr_code = P(xc if xc.size else np.zeros(1), np.int32, C.c_int32)
+        pd.n_expr_const = int(xk.shape[0])
+        pd.expr_const = P(xk if xk.size else np.zeros(1), np.float64, C.c_double)
         pd.tol = prog.tol
         pd.norm = norm_code(norm)
         pd.scale_objectives = int(bool(scale_objectives))

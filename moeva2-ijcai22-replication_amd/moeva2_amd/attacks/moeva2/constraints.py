@@ -16,6 +16,7 @@ import numpy as np
 import pandas as pd
 
 from ..._native import OP
+from . import expr as _expr
 
 
 class ConstraintProgram:
@@ -26,6 +27,8 @@ class ConstraintProgram:
         self.arg: List[List[int]] = []
         self.karg: List[List[float]] = []
         self.pool: List[int] = []
+        self.expr_code: List[int] = []     # bytecode of the EXPR columns, back to back
+        self.expr_const: List[float] = []  # their constants
 
     def add(self, op: str, a=(), k=()):
         a = list(a) + [0] * (4 - len(a))
@@ -41,9 +44,40 @@ class ConstraintProgram:
         self.pool.extend(int(v) for v in second)
         self.add(op, (o0, o1, len(self.pool)), k)
 
+    def add_expr(self, node, n_features: int = None):
+        """Append a user-defined column (MV_OP_EXPR): ``node`` is an expression of
+        ``moeva2_amd.attacks.moeva2.expr``, compiled here; its constants and ``sum_of`` index
+        lists join the program's tables.  op_arg = (code offset, word count, stack depth, 0)."""
+        code, consts, pool = _expr.compile_expr(node, n_features)
+        kmap = []  # the column's constants in the program's table (one entry per bit pattern)
+        for v in consts:
+            bits = float(v).hex()
+            known = [i for i, u in enumerate(self.expr_const) if u.hex() == bits]
+            if not known:
+                self.expr_const.append(float(v))
+            kmap.append(known[0] if known else len(self.expr_const) - 1)
+        p0 = len(self.pool)
+        words = [int(w) for w in code]
+        pc = 0
+        while pc < len(words):  # rebase the inline operands
+            op = words[pc]
+            if op == _expr.OPCODES["K"]:
+                words[pc + 1] = kmap[words[pc + 1]]
+            elif op == _expr.OPCODES["SUMF"]:
+                words[pc + 1] += p0
+                words[pc + 2] += p0
+            pc += 1 + _expr.N_OPERANDS.get(op, 0)
+        self.add("EXPR", (len(self.expr_code), len(words), _expr.stack_depth(words)))
+        self.expr_code.extend(words)
+        self.pool.extend(int(v) for v in pool)
+
     def arrays(self):
         return (np.asarray(self.code, np.int32), np.asarray(self.arg, np.int32).reshape(-1, 4),
                 np.asarray(self.karg, np.float64).reshape(-1, 2), np.asarray(self.pool, np.int32))
+
+    def expr_arrays(self):
+        """(code words int32, constants fp64) of the EXPR columns (both empty without one)."""
+        return np.asarray(self.expr_code, np.int32), np.asarray(self.expr_const, np.float64)
 
     def __len__(self):
         return len(self.code)
@@ -276,6 +310,31 @@ class TabularConstraints(Constraints):
         g = torch.empty((x.shape[0], eng.prog.C), dtype=torch.float64, device=xd.device)
         eng.constraints(xd, g, stream=torch.cuda.current_stream(xd.device))
         return g.cpu().numpy()
+
+
+class ExprConstraints(TabularConstraints):
+    """Constraints given as expressions (``moeva2_amd.attacks.moeva2.expr``): one expression
+    per column over the ML-space row, compiled to MV_OP_EXPR columns, so a new dataset's
+    constraints run on the device without a dedicated op code.  ``evaluate_numpy`` states
+    the same columns on the CPU."""
+
+    def __init__(self, feature_path: str, constraints_path: str, expressions):
+        super().__init__(feature_path, constraints_path)
+        self.expressions = list(expressions)
+        self.device_program()  # compile now: a bad expression fails here, not in the attack
+
+    def device_program(self) -> ConstraintProgram:
+        prog = ConstraintProgram()
+        D = int(self._feature_type.shape[0])
+        for e in self.expressions:
+            prog.add_expr(e, D)
+        return prog
+
+    def get_nb_constraints(self) -> int:
+        return len(self.expressions)
+
+    def evaluate_numpy(self, x: np.ndarray) -> np.ndarray:
+        return _expr.evaluate_numpy(self.expressions, x, tol=self.tol)
 
 
 def _resolve(path_hint: str, name: str) -> str:

@@ -35,14 +35,18 @@ def build_device_program(constraints, with_constraints=True) -> DeviceProgram:
     enc = get_encoder_from_constraints(constraints)
     kind, feat, offs, ohe_feats, mut_feats = enc.device_layout()
     if with_constraints:
-        code, arg, karg, pool = constraints.device_program().arrays()
+        prog = constraints.device_program()
+        code, arg, karg, pool = prog.arrays()
+        xcode, xconst = prog.expr_arrays()
     else:  # host-evaluated constraints: the device program is empty (f3 filled by the host)
         code, arg, karg, pool = (np.zeros(0, np.int32), np.zeros((0, 4), np.int32),
                                  np.zeros((0, 2)), np.zeros(0, np.int32))
+        xcode, xconst = np.zeros(0, np.int32), np.zeros(0)
     return DeviceProgram(D=int(enc.mutable_mask.shape[0]), gene_kind=kind, gene_feat=feat,
                          ohe_offsets=offs, ohe_feats=ohe_feats, mut_feats=mut_feats,
                          op_code=code, op_arg=arg, op_karg=karg, idx_pool=pool,
-                         tol=getattr(constraints, "tol", 1e-3))
+                         tol=getattr(constraints, "tol", 1e-3), expr_code=xcode,
+                         expr_const=xconst)
 
 
 def ml_transform(ml_scaler, x_f):
