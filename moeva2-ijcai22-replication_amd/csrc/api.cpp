@@ -363,7 +363,7 @@ static int build_problem(const HostProblem& h, const HostModel* hm, const std::v
   for (int c = 0; c < V && p.ident; ++c) p.ident = kind[c] != MV_GENE_OHE && feat[c] == mut[c];
   {  // k_vary problem blob: the LDS image of the tables (kernels.h vary_offsets)
     const VaryOff vo = vary_offsets(p);
-    if (gen_lds(vo, false, false, true).total > 160 * 1024 || cons_lds_total(vo) > 160 * 1024)
+    if (gen_lds(vo, false, true).total > 160 * 1024 || cons_lds_total(vo) > 160 * 1024)
       return fail(MV_ERR_ARG, "problem too large for the k_vary LDS workspace");
     std::vector<unsigned char> blob(vo.vb, 0);
     auto put = [&](unsigned off, const void* src, size_t n) {
@@ -1232,11 +1232,7 @@ int mv_attack_run(mv_engine* e, const mv_attack_params* prm, void* stream_) {
   sa.dom_g = e->dom_g;
   sa.dom_stride = e->dom_stride;
   {  // 10-wave survival workgroups when every state fits two workgroups per CU (SurvArgs.wide)
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      cus = 0;
-    (void)hipGetLastError();
+    const int cus = device_cus();  // 0 (query failed): wide = 0
     // 2: small attacks (every state has half a CU or more to itself -- configs[0], the
     // per-GPU share of 8-GPU strong scaling): 16-wave workgroups, so one state's issue-
     // and latency-bound phases interleave four waves per SIMD

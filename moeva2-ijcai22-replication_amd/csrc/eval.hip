@@ -1,19 +1,9 @@
 // Fitness evaluation and variation kernels (gfx950).
 //
-// One generation's candidate rows go through two kernels:
-//  k_vary (one wave per row, small LDS, high occupancy):
-//     [mode 1] two-point crossover + polynomial mutation of the row's parents
-//              (moeva2.py:90-111 -> softmax_crossover.py:17-38 / softmax_mutation.py:20-67
-//              semantics, Philox draws), child written to the population pool;
-//     decode genes -> ML row x_f in LDS (feature_encoder.py:91-124);
-//     encoder MinMax distance f2 (default_problem.py:80-91, utils.py:11-22);
-//     constraint program -> G, f3 (default_problem.py:93-97,128-129);
-//     ML-scaled fp32 row (default_problem.py:119-121) -> scratch xml[row][Dm4].
-//  k_mlp (32-row tiles): the Dense-ReLU chain on MFMA (v_mfma_f32_16x16x4_f32, exact fp32
-//     products), layer 1 over the mutable columns only (immutable columns folded into a
-//     per-state bias), final Dense + softmax on the VALU with its weights in LDS
-//     (classifier.py:23-29) -> f1.
-// k_predict: Classifier.predict_proba on ML rows.   k_setup_states: per-state constants.
+// The row kernels (k_gen + k_cons / k_consx, k_narrow, k_genc), the classifier kernels (k_mlp,
+// k_mlp2, k_mlpr, k_mlpw, k_mlpw32), k_predict, k_constraints, k_decode and k_setup_states.
+// Which instance a launch runs is decided in routes.h (row_route, mlp_route); the launchers at
+// the end of this file switch on that route and row_kernel_kind / mlp_kernel_kind report it.
 //
 // Launch arguments live in constant memory: a ring of RowsArgs slots per device (c_rows),
 // written stream-ordered from pinned host copies.  As by-value kernel arguments the
@@ -21,8 +11,10 @@
 // pointers they hold lose their address space (every access became a flat op); pointers
 // loaded from the constant address space are known to be global.  Only the
 // per-generation scalars (slot, gen, first history row) are passed by value.
+#include <atomic>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 
 #include "check.h"
 #include "engine.h"
@@ -46,7 +38,31 @@ struct ArgRing {
 constexpr int MAX_DEVICES = 64;
 ArgRing g_rings[MAX_DEVICES];
 std::mutex g_ring_mu;
+std::atomic<int> g_cus[MAX_DEVICES];  // CUs per device, 0 until queried
+// CUs of the device in whose ring this thread last staged a slot: the launchers of that slot
+// run on the same device, and need no device query of their own per launch
+thread_local int t_ring_cus = 0;
+
+int cus_of(int dev) {
+  int cus = g_cus[dev].load(std::memory_order_relaxed);
+  if (cus > 0) return cus;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    cus = 0;
+  (void)hipGetLastError();
+  if (cus > 0) g_cus[dev].store(cus, std::memory_order_relaxed);
+  return cus;
+}
 }  // namespace
+
+// CUs of the current device, cached per device; 0 when the query fails.
+int device_cus() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return cus_of(dev);
+}
 
 size_t lds_pad(const char* env) {
   const char* v = std::getenv(env);
@@ -58,6 +74,7 @@ hipError_t stage_rows(const RowsArgs& a, hipStream_t stream, int* slot) {
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
   if (dev < 0 || dev >= MAX_DEVICES) return hipErrorInvalidDevice;
+  t_ring_cus = cus_of(dev);
   std::lock_guard<std::mutex> lock(g_ring_mu);
   ArgRing& r = g_rings[dev];
   if (!r.ready) {
@@ -226,8 +243,8 @@ __device__ __forceinline__ void plan_draws(const RowsArgs& a, const DProblem& p,
 // ML-scaled mutable row for k_mlp (default_problem.py:119-121) and f2, the encoder-MinMax
 // distance (default_problem.py:80-91).
 //
-// Lane l owns genes l + 64t: coalesced 512-B gene loads/stores, its gene-table words (and,
-// REGC, its ML-scaler / encoder coefficients) in registers; the next row's parent genes
+// Lane l owns genes l + 64t: coalesced 512-B gene loads/stores, its gene-table words in
+// registers (the ML-scaler / encoder coefficients in LDS); the next row's parent genes
 // are loaded while the current row is finished.  Two-point crossover draws and the
 // mutations are precomputed for all of a wave's rows at once, one row per lane: mutations
 // are a geometric-gap process (about two Philox draws per row instead of one word per
@@ -242,7 +259,6 @@ __device__ __forceinline__ int gen_rows(const RowsArgs& a, int gen, int hist_row
                                         unsigned char* smem) {
   static_assert(!EARLY || (IDENT && PLAN && !SBX), "early staging: k_genc two-point only");
   constexpr bool FUSED = EARLY;  // the constraints inside the row loop (genc_fused_lds)
-  constexpr bool REGC = GEN_REGC && IDENT && NT <= 8;  // kernels.h gen_regc
   const DProblem& p = a.p;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const RowChunk rc = row_chunk(a.n, rows_wg, wave);
@@ -250,7 +266,7 @@ __device__ __forceinline__ int gen_rows(const RowsArgs& a, int gen, int hist_row
   const int V = p.V, Dm = p.Dm, Dm4 = p.Dm4;
   const bool ev = a.do_eval != 0;
   const VaryOff o = vary_offsets(p);
-  const GenLds L = FUSED ? genc_fused_lds(o, p) : gen_lds(o, REGC, IDENT, ev);
+  const GenLds L = FUSED ? genc_fused_lds(o, p) : gen_lds(o, IDENT, ev);
   const unsigned char* sblob = a.s.sblob + (size_t)b * o.sb;
   // the rows' matings and destinations first: their round trips (the parents come from the
   // previous k_survive) overlap the LDS staging instead of following it
@@ -306,35 +322,21 @@ __device__ __forceinline__ int gen_rows(const RowsArgs& a, int gen, int hist_row
     }
   } else {
     glds_copy(smem + L.b_at, p.vblob + o.b_at, o.b_end - o.b_at, wave, lane);
-    if (ev && !REGC) {
+    if (ev) {
       glds_copy(smem + L.c_at, p.vblob + o.c_at, o.c_end - o.c_at, wave, lane);
       glds_copy(smem + L.e_at, sblob + o.e_at, o.sb - o.e_at, wave, lane);
     }
     if (ev && !IDENT) glds_copy(smem + L.x_at, sblob, o.x_end, wave, lane);
   }
-  // per-lane gene-table words and (REGC) coefficients, straight from HBM meanwhile
+  // per-lane gene-table words, straight from HBM meanwhile
   int ginf[NT];
-  double cS[NT], cM[NT], cE[NT], cN[NT], cX[NT];
   {
     const int* gi = (const int*)(p.vblob + o.ginfo);
-    const double* mS = (const double*)(p.vblob + o.mlS);
-    const double* mM = (const double*)(p.vblob + o.mlM);
-    const double* sE = (const double*)(sblob + o.es);
-    const double* sN = (const double*)(sblob + o.em);
-    const double* sX = (const double*)(sblob + o.x0);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int g = lane + 64 * t;
       const int w = gi[g < V ? g : V - 1];  // unconditional load (see k_cons load_row)
       ginf[t] = g < V ? w : 0;
-      if (REGC) {
-        const bool in = ev && g < Dm4;
-        cS[t] = in ? mS[g] : 0.0;
-        cM[t] = in ? mM[g] : 0.0;
-        cE[t] = in ? sE[g] : 0.0;
-        cN[t] = in ? sN[g] : 0.0;
-        cX[t] = in ? sX[g] : 0.0;
-      }
     }
   }
   __builtin_amdgcn_s_waitcnt(0);
@@ -459,7 +461,7 @@ __device__ __forceinline__ int gen_rows(const RowsArgs& a, int gen, int hist_row
     if (!ev) return;
     float* xo = a.xml + ((size_t)b * a.n + i) * Dm4;
     double acc = 0.0;
-    if (IDENT && !REGC && p.xml_direct) {  // f2 only, branch-free -- every lane
+    if (IDENT && p.xml_direct) {  // f2 only, branch-free -- every lane
       // computes its term from in-range LDS reads and the sum takes +0.0 past Dm (acc >= +0,
       // never -0: the bits are those of the guarded sum)
       // (FUSED: unclamped reads at immediate offsets -- past Dm4 an index reads the next
@@ -496,10 +498,10 @@ __device__ __forceinline__ int gen_rows(const RowsArgs& a, int gen, int hist_row
           float v = 0.f;
           if (j < Dmo) {
             const double xf = x[t];
-            const double es = REGC ? cE[t] : s_es[j], em = REGC ? cN[t] : s_em[j];
-            const double x0 = REGC ? cX[t] : s_x0[j];
+            const double es = s_es[j], em = s_em[j];
+            const double x0 = s_x0[j];
             if (wx) {
-              const double ms = REGC ? cS[t] : s_mlS[j], mm = REGC ? cM[t] : s_mlM[j];
+              const double ms = s_mlS[j], mm = s_mlM[j];
               v = (float)(xf * ms + mm);
             }
             const double d = (xf * es + em) - x0;
@@ -1060,12 +1062,6 @@ __device__ __forceinline__ void last_layer_softmax(const float* in, int ldi, int
   softmax_all(z, nout, mx, prob);
 }
 
-__host__ __device__ inline int max_hidden(const int* dims, int n_layers) {
-  int h = 16;
-  for (int l = 1; l < n_layers; ++l) h = dims[l] > h ? dims[l] : h;
-  return h;
-}
-
 // Dense chain over 32-row tiles of the fp32 ML rows -> f1.
 template <int MAXCT, bool BF>
 __global__ __launch_bounds__(EVAL_T) void k_mlp(int slot, int hist_row0) {
@@ -1605,51 +1601,6 @@ __global__ __launch_bounds__(256, BF ? (CJ == 1 ? 3 : 2) : (DIRECT && CJ == 1 ? 
 #ifndef MV_MLPR_OCC
 #define MV_MLPR_OCC 3  // waves per SIMD of the 16-row instance (<= 168 registers)
 #endif
-// LDS: the ML scaler at the mutable features (mlS, mlM), the final Dense layer, the hidden
-// layers' packed weights and biases (read per tile: from L2 each hidden layer waited out a
-// ~3 k-cycle round trip, MV_MLP_PHASES "hidden" 16.9 k cycles per tile), then per wave its
-// tile's bias1 rows (landed by LDS DMA while layer 0 runs) and its last-hidden-layer rows.
-struct MlprLds {
-  unsigned wl, hw, hb, b1, hs, wst, total;
-  int hld;  // fp32 row stride of a wave's last-hidden-layer rows
-};
-__host__ __device__ inline MlprLds mlpr_lds(const DProblem& p, int rw) {
-  const int nl = p.n_layers;
-  MlprLds L{};
-  L.wl = (unsigned)p.Dm4 * 16;  // mlS, mlM
-  L.hld = p.dims[nl - 1] + 4;
-  L.hw = L.wl + (((unsigned)(p.dims[nl - 1] * p.dims[nl] + p.dims[nl]) * 4 + 15) & ~15u);
-  unsigned w = 0, b = 0;
-  for (int l = 1; l + 1 < nl; ++l) {
-    w += (unsigned)(p.dims[l] * p.dims[l + 1]);
-    b += (unsigned)p.dims[l + 1];
-  }
-  L.hb = L.hw + w * 4;
-  // a wave's bias1 rows are in registers before its last-hidden-layer rows are written: one
-  // per-wave region serves both
-  L.b1 = L.hb + ((b * 4 + 15) & ~15u);
-  L.hs = L.b1;
-  L.wst = (unsigned)rw * 4 * 1024;
-  const unsigned hsz = (unsigned)(rw * 16 * L.hld) * 4;
-  L.wst = L.wst > hsz ? L.wst : hsz;
-  L.total = L.b1 + 4u * L.wst;
-  return L;
-}
-// The shapes k_mlpr takes: IDENT gene rows (xml_direct) of an even gene count (16-B aligned
-// gene pairs), fp32, every MFMA layer's width a multiple of 16 and at most 64, K0 a multiple
-// of 16, at most 8 classes.
-__host__ __device__ inline bool mlpr_ok(const DProblem& p) {
-  // the fp32 ML-row path (LCLD: k_narrow's xml rows, zero-padded to Dm4) takes the XML
-  // instance: the same tiles with the rows' fp32 values as layer 0's operands
-  if (p.mlp_bf16 || !p.mlp2 || p.n_layers < 2 || (p.xml_direct && ((p.Dm & 1) || p.Dm < 2)))
-    return false;
-  for (int l = 0; l + 1 < p.n_layers; ++l)
-    if (!p.Wp[l]) return false;
-  for (int l = 1; l < p.n_layers; ++l)
-    if (p.dims[l] % 16 || p.dims[l] > 64) return false;
-  return p.Dm4 % 16 == 0 && p.dims[p.n_layers] <= 8 && mlpr_lds(p, 2).total <= 96 * 1024;
-}
-
 template <int RW, int NO, bool XML = false>
 __global__ __launch_bounds__(256, RW == 1 ? MV_MLPR_OCC : 2) void k_mlpr(int slot, int hist_row0) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1963,28 +1914,6 @@ __global__ __launch_bounds__(256, RW == 1 ? MV_MLPR_OCC : 2) void k_mlpr(int slo
 // outputs stay fp32 in registers and fold straight into the final Dense (partial sums over
 // each lane's columns, a 16-lane butterfly, then the 8 waves' parts in order) -> softmax ->
 // f1.  Arithmetic = the k_mlp2 bf16 mode's (inputs of every hidden layer rounded to bf16).
-constexpr int MW_ROWS = 64;
-constexpr int MW_T = 512;
-struct MwLds {
-  unsigned h0, h1, part, total;
-  int hs;  // bf16 row stride of the activation buffers
-};
-__host__ __device__ inline MwLds mlpw_lds(const DProblem& p) {
-  const int nl = p.n_layers;
-  int w = (p.Dm4 + 31) & ~31;
-  for (int l = 1; l < nl; ++l) w = p.dims[l] > w ? p.dims[l] : w;
-  MwLds L{};
-  L.hs = w + 8;  // 16-B row padding: consecutive rows start 4 banks apart
-  const unsigned head =
-      256 + (((unsigned)(p.dims[nl - 1] * p.dims[nl] + p.dims[nl]) * 4 + 15) & ~15u);
-  const unsigned hb = (unsigned)MW_ROWS * L.hs * 2;
-  L.h0 = head;
-  L.h1 = L.h0 + hb;
-  L.part = L.h1 + hb;
-  L.total = L.part + (unsigned)(MW_T / 64) * MW_ROWS * p.dims[nl] * 4;
-  return L;
-}
-
 template <int CJ>
 __global__ __launch_bounds__(MW_T) void k_mlpw(int slot, int hist_row0) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -2178,39 +2107,6 @@ __global__ __launch_bounds__(MW_T) void k_mlpw(int slot, int hist_row0) {
 // hidden layer folds into the final Dense from the fp32 registers (as k_mlpw) -> softmax.
 // Replaces the 32-row-tile k_mlp for this shape (each weight byte from L2 now serves 64
 // rows; the tile's MFMAs per k-group no longer wait out their loads).
-struct Mw32Lds {
-  unsigned h, part, total;
-  int hs;  // fp32 row stride of the activation buffer
-};
-__host__ __device__ inline Mw32Lds mlpw32_lds(const DProblem& p) {
-  const int nl = p.n_layers;
-  int w = p.Dm4;
-  for (int l = 1; l < nl; ++l) w = p.dims[l] > w ? p.dims[l] : w;
-  Mw32Lds L{};
-  L.hs = w + 4;  // 16-B row padding: consecutive rows start 4 banks apart
-  const unsigned head =
-      256 + (((unsigned)(p.dims[nl - 1] * p.dims[nl] + p.dims[nl]) * 4 + 15) & ~15u);
-  L.h = head;
-  // the wave partials of the final Dense alias the activation buffer: they are written after
-  // the barrier that retires the last MFMA layer's reads of it, and that layer's outputs stay
-  // in registers (a separate region put 512-wide nets of 8 classes past the CU's LDS and onto
-  // the 32-row-tile k_mlp)
-  L.part = L.h;
-  const unsigned hb = (unsigned)MW_ROWS * L.hs * 4;
-  const unsigned pb = (unsigned)(MW_T / 64) * MW_ROWS * p.dims[nl] * 4;
-  L.total = L.h + (hb > pb ? hb : pb);
-  return L;
-}
-// The shapes k_mlpw32 takes: every MFMA layer's K and N multiples of 16 (Wp packed), at
-// most 4 column tiles per wave (N <= 512: the 256-VGPR budget of two waves per SIMD), LDS
-// within the CU's 160 KiB.
-__host__ __device__ inline bool mlpw32_ok(const DProblem& p) {
-  if (p.n_layers < 2 || !p.Wp[0]) return false;
-  for (int l = 1; l < p.n_layers; ++l)
-    if (p.dims[l] % 16 || p.dims[l] > 512) return false;
-  return p.Dm4 % 16 == 0 && p.dims[p.n_layers] <= 8 && mlpw32_lds(p).total <= 160 * 1024;
-}
-
 template <int CJ>
 __global__ __launch_bounds__(MW_T) void k_mlpw32(int slot, int hist_row0) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -2585,503 +2481,266 @@ __global__ __launch_bounds__(256) void k_setup_states(int slot,
 }
 
 // ---------------------------------------------------------------------------------------
-// Allow up to the full 160 KiB of LDS per workgroup for the dynamic-LDS kernels.
-static void configure_lds_once() {
-  static bool done = false;
-  if (done) return;
-  const int lim = 160 * 1024;
-  const void* fns[] = {(const void*)k_mlp<1, false>, (const void*)k_mlp<2, false>,
-                       (const void*)k_mlp<4, false>, (const void*)k_mlp<8, false>,
-                       (const void*)k_mlp<1, true>,  (const void*)k_mlp<2, true>,
-                       (const void*)k_mlp<4, true>,  (const void*)k_mlp<8, true>,
-                       (const void*)k_constraints<false>, (const void*)k_constraints<true>,
-                       (const void*)k_constraintsx};
-  for (const void* f : fns)
-    (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-  (void)hipGetLastError();
-  done = true;
+// Host side.  Which kernel instance a launch runs is decided in routes.h (row_route,
+// mlp_route); the launchers compute the route once per call and switch on it.
+
+// CUs for the row chunking and the classifier grids (an MI355X's when the query fails)
+static int cus_or_256() {
+  const int n = t_ring_cus > 0 ? t_ring_cus : device_cus();
+  return n > 0 ? n : 256;
 }
 
-template <class K>
-static void allow_lds(K kern) {
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024);
-  (void)hipGetLastError();
+// The development switches (routes.h Switches): the only place their names are read.
+static bool env_zero(const char* name) {
+  const char* s = std::getenv(name);
+  return s && s[0] == '0';
 }
-
-// Rows per k_gen / k_cons workgroup: chunks of at most VARY_ROWS_MAX rows of one state.
-// Among the chunk counts from ceil(n / cap) up, the one whose chunks split evenly over the
-// workgroup's waves (least idle wave-row slots) -- O = 100 gives 5 chunks of 20 rows, 5 per
-// wave, instead of 4 x 25 (waves of 7 and 6 rows): +1.4 % botnet evals/s, +3.3 % with one
-// group.  MV_VARY_ROWS overrides the cap (development sweeps).
-static int vary_rows_per_wg(int n) {
-  static const char* env = std::getenv("MV_VARY_ROWS");
-  static int cap = [] {
-    // row_draws maps a wave's rows onto lanes 4 k + q, plan_draws onto PLAN_MUT k + q: at
-    // most 64 / PLAN_MUT rows per wave
-    constexpr int hi = (64 / PLAN_MUT) * VARY_W < 64 ? (64 / PLAN_MUT) * VARY_W : 64;
-    const int v = env ? std::atoi(env) : VARY_ROWS_MAX;
-    return v < 4 ? 4 : (v > hi ? hi : v);
+static void read_row_switches(Switches& s) {  // per launch: tests flip them in-process
+  s.narrow_off = env_zero("MV_NARROW");
+  s.genc_off = env_zero("MV_GENC");
+}
+static void read_mlp_switches(Switches& s) {
+  static const Switches once = [] {
+    Switches t;
+    t.mlpr_off = env_zero("MV_MLPR");
+    const char* rw = std::getenv("MV_MLPR_RW");
+    t.mlpr_rw = rw ? std::atoi(rw) : 1;
+    t.mlpw32_off = env_zero("MV_MLPW32");
+    t.mlp_co_off = env_zero("MV_MLP_CO");
+    return t;
   }();
-  const int c0 = (n + cap - 1) / cap;
-  if (env) return (n + c0 - 1) / c0;
-  int best = (n + c0 - 1) / c0, waste = INT32_MAX;
-  for (int c = c0; c <= c0 + 3; ++c) {
-    const int r = (n + c - 1) / c;
-    const int w = c * VARY_W * ((r + VARY_W - 1) / VARY_W) - n;
-    if (w < waste) {
-      waste = w;
-      best = r;
-    }
-  }
-  return best;
+  s.mlpr_off = once.mlpr_off;
+  s.mlpr_rw = once.mlpr_rw;
+  s.mlpw32_off = once.mlpw32_off;
+  s.mlp_co_off = once.mlp_co_off;
+  s.mlp_v1 = std::getenv("MV_MLP_V1") != nullptr;
+  s.mlpw = std::getenv("MV_MLPW") != nullptr;
+  s.mlpw_off = std::getenv("MV_MLPW_OFF") != nullptr;
 }
 
-static int device_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    cus = 256;
-  (void)hipGetLastError();
-  return cus;
-}
-
-// Small attacks (states_all x chunks below four workgroups per CU, k_genc's occupancy): the
-// chunks shrink -- down to one row per wave -- until the row launches fill the chip.  Each
-// chunk repeats the workgroup prologue, but with few states the CUs would idle instead, and a
-// generation's row-kernel latency is one chunk's (e.g. 48 botnet states, 8-GPU strong scaling
-// of configs[1]: 240 workgroups of 20 rows -> 1,200 of 4).  Results do not depend on the
-// chunking (every draw is keyed by the row inside its state).
-static int vary_rows_per_wg(int n, int states_all) {
-  int best = vary_rows_per_wg(n);
-  static const bool env = std::getenv("MV_VARY_ROWS") != nullptr;
-  if (env || states_all <= 0) return best;
-  static const int target = 4 * device_cus();
-  if ((long long)states_all * ((n + best - 1) / best) >= target) return best;
-  const int c = (target + states_all - 1) / states_all;  // chunks per state wanted
-  const int r = (n + c - 1) / c;
-  return r < VARY_W ? (best < VARY_W ? best : VARY_W) : (r < best ? r : best);
-}
-
-static int vary_nt(const DProblem& p) {
-  const int m = p.V > p.Dm4 ? p.V : p.Dm4;
-  const int nt = (m + 63) / 64;
-  return nt <= 1 ? 1 : nt <= 2 ? 2 : nt <= 4 ? 4 : nt <= 8 ? 8 : 16;
-}
-
-template <bool IDENT, int NT>
-static hipError_t gen_go(dim3 grid, size_t lds, hipStream_t s, int slot, int gen, int h0, int rw,
-                         bool sbx) {
-  static bool configured = false;
-  if (!configured) {
-    allow_lds(k_gen<IDENT, NT, false>);
-    allow_lds(k_gen<IDENT, NT, true>);
-    configured = true;
-  }
-  if (sbx)
-    MV_LAUNCH((k_gen<IDENT, NT, true>), grid, dim3(VARY_T), lds, s, slot, gen, h0, rw);
-  else
-    MV_LAUNCH((k_gen<IDENT, NT, false>), grid, dim3(VARY_T), lds, s, slot, gen, h0, rw);
+// Launches instance K: its first launch allows it the full 160 KiB of dynamic LDS per
+// workgroup; through MV_LAUNCH, so a profiled launch is stamped kernel-exact.
+template <auto K, class... Args>
+static hipError_t launch_k(dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+  static const bool allowed = [] {
+    (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024);
+    (void)hipGetLastError();
+    return true;
+  }();
+  (void)allowed;
+  MV_LAUNCH(K, grid, block, lds, stream, args...);
   return hipGetLastError();
 }
 
-template <bool IDENT, int NT>
-static hipError_t consx_go(dim3 grid, size_t lds, hipStream_t s, int slot, int h0, int rw) {
-  static bool configured = false;
-  if (!configured) {
-    allow_lds(k_consx<IDENT, NT>);
-    configured = true;
+// ... with a grid of at most the workgroups resident on the chip at this LDS size (the
+// occupancy is cached per instance)
+template <auto K>
+static hipError_t launch_resident(int need, size_t lds, hipStream_t stream, int slot,
+                                  int hist_row0) {
+  static size_t occ_lds = 0;
+  static int occ = 1;
+  if (lds != occ_lds) {  // resident workgroups per CU at this LDS size
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K, 256, lds) != hipSuccess || n < 1)
+      n = 1;
+    (void)hipGetLastError();
+    occ = n;
+    occ_lds = lds;
   }
-  MV_LAUNCH((k_consx<IDENT, NT>), grid, dim3(CONS_T), lds, s, slot, h0, rw);
-  return hipGetLastError();
+  const int cap = occ * cus_or_256();
+  return launch_k<K>(dim3(need < cap ? need : cap), dim3(256), lds, stream, slot, hist_row0);
 }
 
-template <bool FULL, bool IDENT, int NT>
-static hipError_t cons_go(dim3 grid, size_t lds, hipStream_t s, int slot, int h0, int rw) {
-  static bool configured = false;
-  if (!configured) {
-    allow_lds(k_cons<FULL, IDENT, NT>);
-    configured = true;
-  }
-  MV_LAUNCH((k_cons<FULL, IDENT, NT>), grid, dim3(CONS_T), lds, s, slot, h0, rw);
-  return hipGetLastError();
+// f(std::integral_constant<int, N>) for the N of the set that equals n
+template <int... NS, class F>
+static hipError_t dispatch_nt(int n, F&& f) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)((n == NS ? (e = f(std::integral_constant<int, NS>{}), true) : false) || ...);
+  return e;
+}
+template <class F>
+static hipError_t dispatch_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+#define CT(X) decltype(X)::value
+
+static int rows_per_wg(const RowsArgs& a) {
+  static const int cap_override = [] {  // MV_VARY_ROWS (development sweeps)
+    const char* env = std::getenv("MV_VARY_ROWS");
+    const int v = env ? std::atoi(env) : 0;
+    return env ? (v < 1 ? 1 : v) : 0;
+  }();
+  return vary_rows_per_wg(a.n, a.states_all, cus_or_256(), cap_override);
 }
 
-// Narrow rows (LCLD-shaped problems): k_narrow does k_gen's and k_cons's work in one launch
-// (two-point crossover; the SBX option and variation-only launches keep the wave-per-row
-// kernels).  MV_NARROW=0 turns it off (A/B runs).
-static bool use_narrow(const RowsArgs& a) {
-  const char* s = std::getenv("MV_NARROW");  // read per launch: tests flip it in-process
-  return !(s && s[0] == '0') && a.do_eval && narrow_ok(a.p) && !(a.mode == 1 && a.cx_kind == 1) &&
-         !a.p.compact &&      // the compact layout runs on the wave-per-row kernels only
-         a.p.full_ops != 2;   // and so do MV_OP_EXPR columns (k_gen + k_consx)
-}
-
-template <int NV, bool FULL>
-static hipError_t narrow_go(const RowsArgs& a, int slot, int gen, int hist_row0,
-                            hipStream_t stream) {
-  static bool configured = false;
-  if (!configured) {
-    allow_lds(k_narrow<NV, FULL>);
-    configured = true;
-  }
-  const size_t lds = narrow_lds(vary_offsets(a.p), a.p).total;
-  const dim3 grid((unsigned)((a.total + NARROW_T - 1) / NARROW_T));
-  MV_LAUNCH((k_narrow<NV, FULL>), grid, dim3(NARROW_T), lds, stream, slot, gen,
-                     hist_row0);
-  return hipGetLastError();
-}
-
-static hipError_t launch_narrow(const RowsArgs& a, int slot, int gen, int hist_row0,
-                                hipStream_t stream) {
-#define NG(NV) \
-  return a.p.full_ops ? narrow_go<NV, true>(a, slot, gen, hist_row0, stream) \
-                      : narrow_go<NV, false>(a, slot, gen, hist_row0, stream)
-  if (a.p.V <= 8) NG(8);
-  if (a.p.V <= 16) NG(16);
-  NG(32);
-#undef NG
-}
-
-// k_genc (k_gen + k_cons in one launch) for the wave-per-row evaluation of IDENT problems
-// without the LCLD financial ops (the botnet shape).  MV_GENC=0 keeps the two launches.
-// k_genc's genes per lane: the exact ceil(max(V, Dm4) / 64) from 4 to 8 (every unused
-// register slot costs a masked instruction per row in every phase), else 16.
-static int genc_nt(const DProblem& p) {
-  const int m = p.V > p.Dm4 ? p.V : p.Dm4;
-  const int nt = (m + 63) / 64;
-  return nt <= 4 ? 4 : nt <= 8 ? nt : 16;
-}
-
-static bool use_genc(const RowsArgs& a) {
-  const char* s = std::getenv("MV_GENC");  // read per launch: tests flip it in-process
-  return !(s && s[0] == '0') && a.do_eval && a.p.ident && !a.p.full_ops && !use_narrow(a) &&
-         (a.p.V > a.p.Dm4 ? a.p.V : a.p.Dm4) > 128;
-}
-
-template <int NT>
-static hipError_t genc_go(dim3 grid, size_t lds, hipStream_t s, int slot, int gen, int h0, int rw,
-                          bool sbx, bool slim) {
-  static bool configured = false;
-  if (!configured) {
-    allow_lds(k_genc<true, NT, false, false>);
-    allow_lds(k_genc<true, NT, true, false>);
-    allow_lds(k_genc<true, NT, false, true>);
-    allow_lds(k_genc<true, NT, true, true>);
-    configured = true;
-  }
-#define GENC(X, Y) \
-  MV_LAUNCH((k_genc<true, NT, X, Y>), grid, dim3(VARY_T), lds, s, slot, gen, h0, rw)
-  if (sbx) {
-    if (slim)
-      GENC(true, true);
-    else
-      GENC(true, false);
-  } else {
-    if (slim)
-      GENC(false, true);
-    else
-      GENC(false, false);
-  }
-#undef GENC
-  return hipGetLastError();
-}
-
-int row_kernel_kind(const RowsArgs& a) {
-  if (use_narrow(a)) return 1;
-  if (use_genc(a)) return 2;
-  return 0;
-}
-
-hipError_t launch_gen(const RowsArgs& a, int slot, int gen, int hist_row0, hipStream_t stream) {
+static hipError_t run_gen(const RowsArgs& a, const RowRoute& r, int slot, int gen, int hist_row0,
+                          hipStream_t stream) {
   if (a.total <= 0) return hipSuccess;
-  if (use_narrow(a)) return launch_narrow(a, slot, gen, hist_row0, stream);
-  if (use_genc(a)) {
-    const int B = a.total / a.n;
-    const int rw = vary_rows_per_wg(a.n, a.states_all);
-    const dim3 grid(B * ((a.n + rw - 1) / rw));
-    const int nt = genc_nt(a.p);
-    const VaryOff o = vary_offsets(a.p);
-    const bool sbx = a.mode == 1 && a.cx_kind == 1;
-    const GenLds gl = gen_lds(o, gen_regc(a.p, nt), true, true);
-    const size_t lg = sbx ? gen_lds_sbx(gl, nt) : gl.total;
-    const bool slim = a.p.slim != 0;
-    const size_t lc = slim ? cons_lds_slim(o) : cons_lds_total(o);
-    static const size_t pad = lds_pad("MV_LDS_PAD_GENC");
-    const size_t lds = (slim && !sbx ? genc_fused_lds(o, a.p).total : (lg > lc ? lg : lc)) + pad;
-    // k_genc takes mode 1's draws from the variation plan (mv_attack_run's k_survive)
-    if (a.mode == 1 && !(a.plan_hdr && a.plan_mw && a.plan_mu)) return hipErrorInvalidValue;
-    if (nt == 4) return genc_go<4>(grid, lds, stream, slot, gen, hist_row0, rw, sbx, slim);
-    if (nt == 5) return genc_go<5>(grid, lds, stream, slot, gen, hist_row0, rw, sbx, slim);
-    if (nt == 6) return genc_go<6>(grid, lds, stream, slot, gen, hist_row0, rw, sbx, slim);
-    if (nt == 7) return genc_go<7>(grid, lds, stream, slot, gen, hist_row0, rw, sbx, slim);
-    if (nt == 8) return genc_go<8>(grid, lds, stream, slot, gen, hist_row0, rw, sbx, slim);
-    return genc_go<16>(grid, lds, stream, slot, gen, hist_row0, rw, sbx, slim);
+  if (r.kind == ROW_NARROW) {
+    const size_t lds = narrow_lds(vary_offsets(a.p), a.p).total;
+    const dim3 grid((unsigned)((a.total + NARROW_T - 1) / NARROW_T));
+    return dispatch_nt<8, 16, 32>(r.nv, [&](auto NV) {
+      return dispatch_bool(r.full, [&](auto FULL) {
+        return launch_k<k_narrow<CT(NV), CT(FULL)>>(grid, dim3(NARROW_T), lds, stream, slot, gen,
+                                                    hist_row0);
+      });
+    });
   }
   const int B = a.total / a.n;
-  const int rw = vary_rows_per_wg(a.n, a.states_all);
+  const int rw = rows_per_wg(a);
   const dim3 grid(B * ((a.n + rw - 1) / rw));
-  const int nt = vary_nt(a.p);
-  const bool ident = a.p.ident != 0;
-  const bool sbx = a.mode == 1 && a.cx_kind == 1;
-  const GenLds gl = gen_lds(vary_offsets(a.p), gen_regc(a.p, nt), ident, a.do_eval != 0);
-  const size_t lds = sbx ? gen_lds_sbx(gl, nt) : gl.total;
-#define GEN(I, N) return gen_go<I, N>(grid, lds, stream, slot, gen, hist_row0, rw, sbx)
-  if (ident) {
-    if (nt == 1) GEN(true, 1);
-    if (nt == 2) GEN(true, 2);
-    if (nt == 4) GEN(true, 4);
-    if (nt == 8) GEN(true, 8);
-    GEN(true, 16);
+  const VaryOff o = vary_offsets(a.p);
+  if (r.kind == ROW_GENC) {
+    if (r.plan_missing) return hipErrorInvalidValue;
+    const GenLds gl = gen_lds(o, true, true);
+    const size_t lg = r.sbx ? gen_lds_sbx(gl, r.nt) : gl.total;
+    const size_t lc = r.slim ? cons_lds_slim(o) : cons_lds_total(o);
+    static const size_t pad = lds_pad("MV_LDS_PAD_GENC");
+    const size_t lds =
+        (r.slim && !r.sbx ? genc_fused_lds(o, a.p).total : (lg > lc ? lg : lc)) + pad;
+    return dispatch_nt<4, 5, 6, 7, 8, 16>(r.nt, [&](auto NT) {
+      return dispatch_bool(r.sbx, [&](auto SBX) {
+        return dispatch_bool(r.slim, [&](auto SLIM) {
+          return launch_k<k_genc<true, CT(NT), CT(SBX), CT(SLIM)>>(
+              grid, dim3(VARY_T), lds, stream, slot, gen, hist_row0, rw);
+        });
+      });
+    });
   }
-  if (nt == 1) GEN(false, 1);
-  if (nt == 2) GEN(false, 2);
-  if (nt == 4) GEN(false, 4);
-  if (nt == 8) GEN(false, 8);
-  GEN(false, 16);
-#undef GEN
+  const GenLds gl = gen_lds(o, r.ident, a.do_eval != 0);
+  const size_t lds = r.sbx ? gen_lds_sbx(gl, r.nt) : gl.total;
+  return dispatch_nt<1, 2, 4, 8, 16>(r.nt, [&](auto NT) {
+    return dispatch_bool(r.ident, [&](auto IDENT) {
+      return dispatch_bool(r.sbx, [&](auto SBX) {
+        return launch_k<k_gen<CT(IDENT), CT(NT), CT(SBX)>>(grid, dim3(VARY_T), lds, stream, slot,
+                                                           gen, hist_row0, rw);
+      });
+    });
+  });
+}
+
+static hipError_t run_cons(const RowsArgs& a, const RowRoute& r, int slot, int hist_row0,
+                           hipStream_t stream) {
+  // CONS_NONE: done by k_narrow / k_genc in run_gen, or a variation-only launch
+  if (a.total <= 0 || r.cons == CONS_NONE) return hipSuccess;
+  const int B = a.total / a.n;
+  const int rw = rows_per_wg(a);
+  const dim3 grid(B * ((a.n + rw - 1) / rw));
+  const size_t lds = cons_lds_total(vary_offsets(a.p));
+  return dispatch_nt<1, 2, 4, 8, 16>(r.nt, [&](auto NT) {
+    if (r.cons == CONS_EXPR)
+      return dispatch_bool(r.ident, [&](auto IDENT) {
+        return launch_k<k_consx<CT(IDENT), CT(NT)>>(grid, dim3(CONS_T), lds, stream, slot,
+                                                    hist_row0, rw);
+      });
+    if (r.cons == CONS_FULL)
+      return launch_k<k_cons<true, false, CT(NT)>>(grid, dim3(CONS_T), lds, stream, slot,
+                                                   hist_row0, rw);
+    return dispatch_bool(r.ident, [&](auto IDENT) {
+      return launch_k<k_cons<false, CT(IDENT), CT(NT)>>(grid, dim3(CONS_T), lds, stream, slot,
+                                                        hist_row0, rw);
+    });
+  });
+}
+
+static RowRoute route_rows(const RowsArgs& a) {
+  Switches sw;
+  read_row_switches(sw);
+  return row_route(a, sw);
+}
+
+int row_kernel_kind(const RowsArgs& a) { return route_rows(a).kind; }
+
+hipError_t launch_gen(const RowsArgs& a, int slot, int gen, int hist_row0, hipStream_t stream) {
+  return run_gen(a, route_rows(a), slot, gen, hist_row0, stream);
 }
 
 hipError_t launch_cons(const RowsArgs& a, int slot, int hist_row0, hipStream_t stream) {
-  if (a.total <= 0 || !a.do_eval) return hipSuccess;
-  if (use_narrow(a)) return hipSuccess;  // done by k_narrow in launch_gen
-  if (use_genc(a)) return hipSuccess;    // done by k_genc in launch_gen
-  const int B = a.total / a.n;
-  const int rw = vary_rows_per_wg(a.n, a.states_all);
-  const dim3 grid(B * ((a.n + rw - 1) / rw));
-  const int nt = vary_nt(a.p);
-  const size_t lds = cons_lds_total(vary_offsets(a.p));
-  if (a.p.full_ops == 2) {  // MV_OP_EXPR columns: the interpreter instances
-#define CONSX(I, N) return consx_go<I, N>(grid, lds, stream, slot, hist_row0, rw)
-    if (a.p.ident) {
-      if (nt == 1) CONSX(true, 1);
-      if (nt == 2) CONSX(true, 2);
-      if (nt == 4) CONSX(true, 4);
-      if (nt == 8) CONSX(true, 8);
-      CONSX(true, 16);
-    }
-    if (nt == 1) CONSX(false, 1);
-    if (nt == 2) CONSX(false, 2);
-    if (nt == 4) CONSX(false, 4);
-    if (nt == 8) CONSX(false, 8);
-    CONSX(false, 16);
-#undef CONSX
-  }
-#define CONS(F, I, N) return cons_go<F, I, N>(grid, lds, stream, slot, hist_row0, rw)
-  if (a.p.full_ops) {  // LCLD programs: one-hot genes, few genes
-    if (nt == 1) CONS(true, false, 1);
-    if (nt == 2) CONS(true, false, 2);
-    if (nt == 4) CONS(true, false, 4);
-    if (nt == 8) CONS(true, false, 8);
-    CONS(true, false, 16);
-  }
-  if (a.p.ident) {
-    if (nt == 1) CONS(false, true, 1);
-    if (nt == 2) CONS(false, true, 2);
-    if (nt == 4) CONS(false, true, 4);
-    if (nt == 8) CONS(false, true, 8);
-    CONS(false, true, 16);
-  }
-  if (nt == 1) CONS(false, false, 1);
-  if (nt == 2) CONS(false, false, 2);
-  if (nt == 4) CONS(false, false, 4);
-  if (nt == 8) CONS(false, false, 8);
-  CONS(false, false, 16);
-#undef CONS
+  return run_cons(a, route_rows(a), slot, hist_row0, stream);
 }
 
 // Variation + evaluation of the rows in the per-phase chain: k_gen then k_cons.
 hipError_t launch_vary(const RowsArgs& a, int slot, int gen, int hist_row0,
                        hipStream_t stream) {
-  hipError_t e = launch_gen(a, slot, gen, hist_row0, stream);
+  const RowRoute r = route_rows(a);
+  hipError_t e = run_gen(a, r, slot, gen, hist_row0, stream);
   if (e != hipSuccess) return e;
-  return launch_cons(a, slot, hist_row0, stream);
+  return run_cons(a, r, slot, hist_row0, stream);
 }
 
-static int cu_count() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
+static MlpRoute route_mlp(const DProblem& p) {
+  Switches sw;
+  read_mlp_switches(sw);
+  return mlp_route(p, sw);
 }
 
-template <int CJ, bool BF, bool DIRECT, bool CO>
-static hipError_t mlp2_go3(const RowsArgs& a, int slot, int hist_row0, hipStream_t stream) {
-  static bool configured = false;
-  static size_t occ_lds = 0;
-  static int occ = 2;
-  if (!configured) {
-    allow_lds(k_mlp2<CJ, BF, DIRECT, CO>);
-    configured = true;
-  }
-  static const size_t pad = lds_pad("MV_LDS_PAD_MLP");
-  const size_t lds = mlp2_lds(a.p) + pad;
-  if (lds != occ_lds) {  // resident workgroups per CU at this LDS size
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_mlp2<CJ, BF, DIRECT, CO>, 256, lds) != hipSuccess ||
-        n < 1)
-      n = 1;
-    (void)hipGetLastError();
-    occ = n;
-    occ_lds = lds;
-  }
-  const int ntiles = (a.total + M2_ROWS - 1) / M2_ROWS;
-  const int grid = ntiles < occ * cu_count() ? ntiles : occ * cu_count();
-  MV_LAUNCH((k_mlp2<CJ, BF, DIRECT, CO>), dim3(grid), dim3(256), lds, stream, slot,
-                     hist_row0);
-  return hipGetLastError();
-}
-
-template <int CJ, bool BF>
-static hipError_t mlp2_go(const RowsArgs& a, int slot, int hist_row0, hipStream_t stream) {
-  // CO: the fp32 path's lane-contiguous gene staging (rows of an even gene count start
-  // 16-B aligned in the pool); MV_MLP_CO=0 turns it off (A/B)
-  static const bool co_env = !(std::getenv("MV_MLP_CO") && std::getenv("MV_MLP_CO")[0] == '0');
-  if (a.p.xml_direct && !BF && co_env && (a.p.Dm & 1) == 0)
-    return mlp2_go3<CJ, BF, true, true>(a, slot, hist_row0, stream);
-  return a.p.xml_direct ? mlp2_go3<CJ, BF, true, false>(a, slot, hist_row0, stream)
-                        : mlp2_go3<CJ, BF, false, false>(a, slot, hist_row0, stream);
-}
-
-template <int RW, int NO, bool XML = false>
-static hipError_t mlpr_go(const RowsArgs& a, int slot, int hist_row0, hipStream_t stream) {
-  static size_t occ_lds = 0;
-  static int occ = 1;
-  const size_t lds = mlpr_lds(a.p, RW).total;
-  if (lds != occ_lds) {  // resident workgroups per CU at this LDS size
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_mlpr<RW, NO, XML>, 256, lds) != hipSuccess ||
-        n < 1)
-      n = 1;
-    (void)hipGetLastError();
-    occ = n;
-    occ_lds = lds;
-  }
-  const int ntiles = (a.total + 16 * RW - 1) / (16 * RW);
-  const int need = (ntiles + 3) / 4;
-  const int grid = need < occ * cu_count() ? need : occ * cu_count();
-  MV_LAUNCH((k_mlpr<RW, NO, XML>), dim3(grid), dim3(256), lds, stream, slot, hist_row0);
-  return hipGetLastError();
-}
-
-// k_mlpr's rows per wave tile: MV_MLPR_RW=1 (16) or 2 (32, default)
-static bool use_mlpr(const DProblem& p) {
-  static const bool off = std::getenv("MV_MLPR") && std::getenv("MV_MLPR")[0] == '0';
-  return !off && mlpr_ok(p);
-}
-static int mlpr_rw() {
-  static const int rw = std::getenv("MV_MLPR_RW") ? std::atoi(std::getenv("MV_MLPR_RW")) : 1;
-  return rw == 1 ? 1 : 2;
-}
-
-template <int CJ>
-static hipError_t mlpw_go(const RowsArgs& a, int slot, int hist_row0, hipStream_t stream) {
-  static bool configured = false;
-  if (!configured) {
-    allow_lds(k_mlpw<CJ>);
-    configured = true;
-  }
-  const size_t lds = mlpw_lds(a.p).total;
-  const int ntiles = (a.total + MW_ROWS - 1) / MW_ROWS;
-  const int grid = ntiles < cu_count() ? ntiles : cu_count();  // one 133-KiB workgroup per CU
-  MV_LAUNCH((k_mlpw<CJ>), dim3(grid), dim3(MW_T), lds, stream, slot, hist_row0);
-  return hipGetLastError();
-}
-
-template <int CJ>
-static hipError_t mlpw32_go(const RowsArgs& a, int slot, int hist_row0, hipStream_t stream) {
-  static bool configured = false;
-  if (!configured) {
-    allow_lds(k_mlpw32<CJ>);
-    configured = true;
-  }
-  const size_t lds = mlpw32_lds(a.p).total;
-  const int ntiles = (a.total + MW_ROWS - 1) / MW_ROWS;
-  const int grid = ntiles < cu_count() ? ntiles : cu_count();  // one workgroup per CU
-  MV_LAUNCH((k_mlpw32<CJ>), dim3(grid), dim3(MW_T), lds, stream, slot, hist_row0);
-  return hipGetLastError();
-}
-
-// fp32 wide classifiers (hidden widths above k_mlp2's 128) on k_mlpw32; MV_MLPW32=0 keeps
-// the 32-row-tile k_mlp (A/B)
-static bool use_mlpw32(const DProblem& p) {
-  static const bool off = std::getenv("MV_MLPW32") && std::getenv("MV_MLPW32")[0] == '0';
-  return !off && !p.mlp_bf16 && mlpw32_ok(p);
-}
-
-// launch_mlp's choice for a problem: 0 k_mlp, 1 k_mlp2 reading the genes (xml_direct),
-// 2 k_mlp2 reading the fp32 ML rows, 4 k_mlpw (bf16), 5 k_mlpw32 (fp32 wide), -1 no model
-// (3, k_mlp2x, was retired), 6 k_mlpr (gene-reading, hidden widths <= 64)
-int mlp_kernel_kind(const DProblem& p) {
-  if (p.n_layers == 0) return -1;
-  if (use_mlpr(p)) return p.xml_direct ? 6 : 7;
-  if (p.mlp2 && !std::getenv("MV_MLP_V1") && !(p.mlp_bf16 && std::getenv("MV_MLPW")))
-    return p.xml_direct ? 1 : 2;
-  if (p.mlp_bf16 && mlpw_lds(p).total <= 160 * 1024 && !std::getenv("MV_MLPW_OFF")) return 4;
-  if (use_mlpw32(p)) return 5;
-  return 0;
-}
+int mlp_kernel_kind(const DProblem& p) { return route_mlp(p).kind; }
 
 hipError_t launch_mlp(const RowsArgs& a, int slot, int hist_row0, hipStream_t stream) {
-  if (a.total <= 0 || a.p.n_layers == 0) return hipSuccess;  // model-less: f1 from the host
-  if (use_mlpr(a.p) && !a.p.xml_direct)  // the fp32 ML rows (LCLD)
-    return a.p.dims[a.p.n_layers] <= 2 ? mlpr_go<1, 2, true>(a, slot, hist_row0, stream)
-                                       : mlpr_go<1, 8, true>(a, slot, hist_row0, stream);
-  if (use_mlpr(a.p)) {
-    if (a.p.dims[a.p.n_layers] <= 2)
-      return mlpr_rw() == 1 ? mlpr_go<1, 2>(a, slot, hist_row0, stream)
-                            : mlpr_go<2, 2>(a, slot, hist_row0, stream);
-    return mlpr_rw() == 1 ? mlpr_go<1, 8>(a, slot, hist_row0, stream)
-                          : mlpr_go<2, 8>(a, slot, hist_row0, stream);
+  if (a.total <= 0) return hipSuccess;
+  const DProblem& p = a.p;
+  const MlpRoute r = route_mlp(p);
+  switch (r.kind) {
+    case MLP_NONE:
+      return hipSuccess;  // model-less: f1 from the host
+    case MLPR_GENES:
+    case MLPR_ROWS: {
+      const size_t lds = mlpr_lds(p, r.rw).total;
+      const int ntiles = (a.total + 16 * r.rw - 1) / (16 * r.rw);
+      const int need = (ntiles + 3) / 4;
+#define MLPR(RW, NO, XML) launch_resident<k_mlpr<RW, NO, XML>>(need, lds, stream, slot, hist_row0)
+      if (r.xml) return r.no == 2 ? MLPR(1, 2, true) : MLPR(1, 8, true);
+      if (r.rw == 1) return r.no == 2 ? MLPR(1, 2, false) : MLPR(1, 8, false);
+      return r.no == 2 ? MLPR(2, 2, false) : MLPR(2, 8, false);
+#undef MLPR
+    }
+    case MLP2_GENES:
+    case MLP2_ROWS: {
+      static const size_t pad = lds_pad("MV_LDS_PAD_MLP");
+      const size_t lds = mlp2_lds(p) + pad;
+      const int ntiles = (a.total + M2_ROWS - 1) / M2_ROWS;
+      return dispatch_nt<1, 2>(r.cj, [&](auto CJ) {
+#define MLP2(BF, DIRECT, CO) \
+  launch_resident<k_mlp2<CT(CJ), BF, DIRECT, CO>>(ntiles, lds, stream, slot, hist_row0)
+        // (the route gives CO to fp32 only; the bf16 CO instance stays in the library as before)
+        if (r.co) return dispatch_bool(r.bf, [&](auto BF) { return MLP2(CT(BF), true, true); });
+        if (r.bf) return r.direct ? MLP2(true, true, false) : MLP2(true, false, false);
+        return r.direct ? MLP2(false, true, false) : MLP2(false, false, false);
+#undef MLP2
+      });
+    }
+    case MLPW: {
+      const size_t lds = mlpw_lds(p).total;
+      const int ntiles = (a.total + MW_ROWS - 1) / MW_ROWS;
+      const int cus = cus_or_256();
+      const dim3 grid(ntiles < cus ? ntiles : cus);  // one 133-KiB workgroup per CU
+      return dispatch_nt<1, 2, 4>(r.cj, [&](auto CJ) {
+        return launch_k<k_mlpw<CT(CJ)>>(grid, dim3(MW_T), lds, stream, slot, hist_row0);
+      });
+    }
+    case MLPW32: {
+      const size_t lds = mlpw32_lds(p).total;
+      const int ntiles = (a.total + MW_ROWS - 1) / MW_ROWS;
+      const int cus = cus_or_256();
+      const dim3 grid(ntiles < cus ? ntiles : cus);  // one workgroup per CU
+      return dispatch_nt<1, 2, 4>(r.cj, [&](auto CJ) {
+        return launch_k<k_mlpw32<CT(CJ)>>(grid, dim3(MW_T), lds, stream, slot, hist_row0);
+      });
+    }
+    default: {  // MLP_V1
+      const int nl = p.n_layers;
+      const size_t lds =
+          mlp_lds_bytes(p.Dm4, max_hidden(p.dims, nl), p.dims[nl - 1], p.dims[nl]);
+      const dim3 grid((a.total + EVAL_TR - 1) / EVAL_TR);
+      return dispatch_nt<1, 2, 4, 8>(r.maxct, [&](auto M) {
+        return dispatch_bool(r.bf, [&](auto BF) {
+          return launch_k<k_mlp<CT(M), CT(BF)>>(grid, dim3(EVAL_T), lds, stream, slot,
+                                                hist_row0);
+        });
+      });
+    }
   }
-  // (MV_MLPW=1: the bf16 mode runs k_mlpw for narrow nets too -- development A/B)
-  if (a.p.mlp2 && !std::getenv("MV_MLP_V1") && !(a.p.mlp_bf16 && std::getenv("MV_MLPW"))) {
-    if (a.p.mlp_bf16)
-      return mlp2_hmax(a.p) <= 64 ? mlp2_go<1, true>(a, slot, hist_row0, stream)
-                                  : mlp2_go<2, true>(a, slot, hist_row0, stream);
-    return mlp2_hmax(a.p) <= 64 ? mlp2_go<1, false>(a, slot, hist_row0, stream)
-                                : mlp2_go<2, false>(a, slot, hist_row0, stream);
-  }
-  if (a.p.mlp_bf16 && mlpw_lds(a.p).total <= 160 * 1024 && !std::getenv("MV_MLPW_OFF")) {
-    const int hm = max_hidden(a.p.dims, a.p.n_layers);
-    return hm <= 128 ? mlpw_go<1>(a, slot, hist_row0, stream)
-                     : hm <= 256 ? mlpw_go<2>(a, slot, hist_row0, stream)
-                                 : mlpw_go<4>(a, slot, hist_row0, stream);
-  }
-  if (use_mlpw32(a.p)) {
-    const int hm = max_hidden(a.p.dims, a.p.n_layers);
-    return hm <= 128 ? mlpw32_go<1>(a, slot, hist_row0, stream)
-                     : hm <= 256 ? mlpw32_go<2>(a, slot, hist_row0, stream)
-                                 : mlpw32_go<4>(a, slot, hist_row0, stream);
-  }
-  configure_lds_once();
-  const int nl = a.p.n_layers;
-  const int hmax = max_hidden(a.p.dims, nl);
-  const size_t lds = mlp_lds_bytes(a.p.Dm4, hmax, a.p.dims[nl - 1], a.p.dims[nl]);
-  const dim3 grid((a.total + EVAL_TR - 1) / EVAL_TR);
-  const int nct = hmax / 16;
-#define MLP(M)                                                                           \
-  {                                                                                      \
-    if (a.p.mlp_bf16)                                                                    \
-      MV_LAUNCH((k_mlp<M, true>), grid, dim3(EVAL_T), lds, stream, slot, hist_row0); \
-    else                                                                                 \
-      MV_LAUNCH((k_mlp<M, false>), grid, dim3(EVAL_T), lds, stream, slot, hist_row0); \
-  }
-  if (nct <= 4)
-    MLP(1)
-  else if (nct <= 8)
-    MLP(2)
-  else if (nct <= 16)
-    MLP(4)
-  else
-    MLP(8)
-#undef MLP
-  return hipGetLastError();
 }
 
 hipError_t launch_rows(const RowsArgs& a, int slot, int gen, int hist_row0,
@@ -3091,55 +2750,35 @@ hipError_t launch_rows(const RowsArgs& a, int slot, int gen, int hist_row0,
   return launch_mlp(a, slot, hist_row0, stream);
 }
 
-template <int RT>
-static hipError_t predict_go(const MlpArgs& a, int nct, size_t lds, hipStream_t stream) {
-  static bool configured = false;
-  if (!configured) {
-    allow_lds(k_predict<1, RT>);
-    allow_lds(k_predict<2, RT>);
-    allow_lds(k_predict<4, RT>);
-    allow_lds(k_predict<8, RT>);
-    configured = true;
-  }
-  const dim3 grid((a.n + 16 * RT - 1) / (16 * RT));
-  if (nct <= 4)
-    MV_LAUNCH((k_predict<1, RT>), grid, dim3(EVAL_T), lds, stream, a);
-  else if (nct <= 8)
-    MV_LAUNCH((k_predict<2, RT>), grid, dim3(EVAL_T), lds, stream, a);
-  else if (nct <= 16)
-    MV_LAUNCH((k_predict<4, RT>), grid, dim3(EVAL_T), lds, stream, a);
-  else
-    MV_LAUNCH((k_predict<8, RT>), grid, dim3(EVAL_T), lds, stream, a);
-  return hipGetLastError();
-}
-
 hipError_t launch_predict(const MlpArgs& a, hipStream_t stream) {
   if (a.n <= 0) return hipSuccess;
   const int nl = a.n_layers;
   const int hmax = max_hidden(a.dims, nl);
-  const int nct = hmax / 16;
+  auto go = [&](auto RT, size_t lds) {
+    const dim3 grid((a.n + 16 * CT(RT) - 1) / (16 * CT(RT)));
+    return dispatch_nt<1, 2, 4, 8>(mlp_maxct(hmax), [&](auto M) {
+      return launch_k<k_predict<CT(M), CT(RT)>>(grid, dim3(EVAL_T), lds, stream, a);
+    });
+  };
   // 32-row tiles when they fit the LDS, else 16-row tiles (e.g. 756-512-... models)
   const size_t lds32 = predict_lds_bytes(a.D4, hmax, a.dims[nl - 1], a.dims[nl], 32);
-  if (lds32 <= 160 * 1024) return predict_go<2>(a, nct, lds32, stream);
+  if (lds32 <= 160 * 1024) return go(std::integral_constant<int, 2>{}, lds32);
   const size_t lds16 = predict_lds_bytes(a.D4, hmax, a.dims[nl - 1], a.dims[nl], 16);
   if (lds16 > 160 * 1024) return hipErrorInvalidValue;
-  return predict_go<1>(a, nct, lds16, stream);
+  return go(std::integral_constant<int, 1>{}, lds16);
 }
 
 hipError_t launch_constraints(const DProblem& hp, int slot, int n, const double* x,
                               double* G, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
-  configure_lds_once();
   const size_t lds = (size_t)4 * hp.D * sizeof(double);
   const dim3 grid((n + 3) / 4);
-  if (hp.full_ops == 2)
-    MV_LAUNCH(k_constraintsx, grid, dim3(256), lds, stream, slot, n, x, G);
-  else if (hp.full_ops)
-    MV_LAUNCH(k_constraints<true>, grid, dim3(256), lds, stream, slot, n, x, G);
-  else
-    MV_LAUNCH(k_constraints<false>, grid, dim3(256), lds, stream, slot, n, x, G);
-  return hipGetLastError();
+  if (hp.full_ops == 2) return launch_k<k_constraintsx>(grid, dim3(256), lds, stream, slot, n, x, G);
+  if (hp.full_ops)
+    return launch_k<k_constraints<true>>(grid, dim3(256), lds, stream, slot, n, x, G);
+  return launch_k<k_constraints<false>>(grid, dim3(256), lds, stream, slot, n, x, G);
 }
+#undef CT
 
 MV_DEFINE_TAKE_CHECKS(take_checks_eval)
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "engine.h"
+#include "routes.h"
 
 namespace mv {
 
@@ -122,22 +123,16 @@ __host__ __device__ inline VaryOff vary_offsets(const DProblem& p) {
   o.rbs = (unsigned)(((size_t)p.Dm + 63) / 64 * 64 * 8);
   return o;
 }
-// k_gen keeps the ML-scaler / encoder coefficients of its genes in registers for IDENT
-// problems with at most 8 genes per lane (no LDS staging of regions C and E then).
-constexpr bool GEN_REGC = false;  // k_gen: coefficients in registers (true) or LDS (false)
-__host__ __device__ inline bool gen_regc(const DProblem& p, int nt) {
-  return GEN_REGC && p.ident && nt <= 8;
-}
 // k_gen LDS: region B [, C, E] [, X + one row per wave for one-hot decoding]
 struct GenLds {
   unsigned b_at, c_at, e_at, x_at, rows_at, total;
 };
-__host__ __device__ inline GenLds gen_lds(const VaryOff& o, bool regc, bool ident, bool eval) {
+__host__ __device__ inline GenLds gen_lds(const VaryOff& o, bool ident, bool eval) {
   GenLds l{};
   unsigned at = 0;
   l.b_at = at;
   at += o.b_end - o.b_at;
-  if (eval && !regc) {
+  if (eval) {
     l.c_at = at;
     at += o.c_end - o.c_at;
     l.e_at = at;
@@ -202,6 +197,8 @@ __host__ __device__ inline size_t predict_lds_bytes(int D4, int hmax, int Klast,
 // by a launch (GENC, MLP, SURV), to measure how the chain's throughput depends on each
 // kernel's LDS footprint (co-residency on a CU).  0 when unset.
 size_t lds_pad(const char* env);
+// CUs of the current device (cached per device); 0 when the query fails
+int device_cus();
 
 hipError_t launch_predict(const MlpArgs& a, hipStream_t stream);
 hipError_t launch_decode(const DProblem& p, const DStates& s, int B, int n, const double* genes,
@@ -217,6 +214,7 @@ hipError_t launch_gen(const RowsArgs& a, int slot, int gen, int hist_row0, hipSt
 // Which kernels launch_gen / launch_cons run for these rows: 0 k_gen + k_cons, 1 k_narrow
 // (launch_cons is empty), 2 k_genc (launch_cons is empty)
 int row_kernel_kind(const RowsArgs& a);
+// mv_get_mlp_kernel's kind of launch_mlp's route (routes.h MlpKind)
 int mlp_kernel_kind(const DProblem& p);
 hipError_t launch_cons(const RowsArgs& a, int slot, int hist_row0, hipStream_t stream);
 hipError_t launch_vary(const RowsArgs& a, int slot, int gen, int hist_row0,

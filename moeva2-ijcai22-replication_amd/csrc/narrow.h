@@ -21,8 +21,8 @@
 namespace mv {
 
 constexpr int NARROW_T = 128;    // threads per k_narrow workgroup (2 waves, 128 rows)
-constexpr int NARROW_MAXV = 32;  // genes per row held in registers
-constexpr int NARROW_MAXF = 64;  // mutable features (Dm4) and constraint ops
+// (NARROW_MAXV genes per row in registers, NARROW_MAXF mutable features and constraint ops:
+// routes.h narrow_ok)
 
 // LDS: regions A (op program), B (gene tables), C (ML scaler), the feature -> mutable-slot
 // map, then per wave the mutable features of its 64 rows as [Dm][64] doubles.
@@ -44,11 +44,6 @@ __host__ __device__ inline NarrowLds narrow_lds(const VaryOff& o, const DProblem
   at += (NARROW_T / 64) * (unsigned)p.Dm * 64 * 8;
   l.total = at;
   return l;
-}
-
-__host__ __device__ inline bool narrow_ok(const DProblem& p) {
-  return p.V <= NARROW_MAXV && p.Dm4 <= NARROW_MAXF && p.C <= NARROW_MAXF &&
-         p.n_sumdiff == 0 && p.Dm >= 1;
 }
 
 // A lane's row: mutable features from its LDS column, immutable ones from x_init.

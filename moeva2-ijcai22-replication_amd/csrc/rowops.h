@@ -771,11 +771,6 @@ constexpr int M2_ROWS = 64;
 constexpr int M2_ALD = 72;  // layer-0 chunk row stride (floats): 8 mod 64 makes the MFMA A-operand
                             // ds_read_b128 groups conflict-free (68 was 2-way in half the groups)
 
-__host__ __device__ inline int mlp2_hmax(const DProblem& p) {
-  int h = 16;
-  for (int l = 1; l < p.n_layers; ++l) h = p.dims[l] > h ? p.dims[l] : h;
-  return h;
-}
 // head: row states (256 B), the final layer's weights and bias, the hidden layers' biases
 __host__ __device__ inline int mlp2_hidden_bias_floats(const DProblem& p) {
   int n = 0;

@@ -14,9 +14,11 @@ classes, and the widths at which a kernel's guards change side:
     restatement of the bf16 arithmetic.
 
 Each test asserts the kernel kind the engine reports, so a routing change cannot move a test
-onto another kernel unnoticed.  The fp32 k_mlp fallback is reachable only through the
-development switches (MV_MLPR=0, MV_MLPW32=0, MV_MLP_V1, ...) with the shipped width limits
-and is not covered here."""
+onto another kernel unnoticed.  The k_mlp fallback is not covered here.  Besides the
+development switches (MV_MLPW32=0, MV_MLPW_OFF) it takes the nets no other kernel fits
+(tests/test_routes_cpu.py pins the selection): hidden widths that are no multiple of 16 or
+above 512, wide nets of more than 8 classes, and 512-wide nets over 640 or more mutable
+features, whose k_mlpw32 tile passes the CU's LDS."""
 import dataclasses
 
 import numpy as np

@@ -1,0 +1,143 @@
+"""The route table of csrc/routes.h, checked without a GPU: tests/native/routes_check.cpp fills
+DProblem / RowsArgs by hand and prints which kernel instance row_route / mlp_route pick and how
+vary_rows_per_wg chunks the rows; the lines must equal EXPECTED.
+
+EXPECTED was printed by this program on the commit that moved the launchers' own conditions
+into routes.h unchanged, so it records what launch_gen / launch_cons / launch_mlp did before
+they consumed the route.  A change to a line is a change of product routing (or of a
+development switch) and needs its own reason; the GPU route tests
+(tests/test_gpu_classifier_routes.py, test_gpu_parity.py) trust the kind this table pins.
+
+Columns: mlp kind = mv_get_mlp_kernel (-1 none, 0 k_mlp, 1 / 2 k_mlp2 genes / ML rows, 4 k_mlpw,
+5 k_mlpw32, 6 / 7 k_mlpr genes / ML rows); row kind = mv_get_row_kernel (0 k_gen + k_cons,
+1 k_narrow, 2 k_genc); cons = 0 none, 1 k_cons, 2 k_cons<FULL>, 3 k_consx.
+
+What the table shows beyond the routes the GPU tests run:
+  * k_mlp (kind 0) is product-reachable: fp32 nets whose k_mlpw32 tile passes the CU's 160 KiB
+    (512-wide with Dm4 >= 640), hidden widths that are no multiple of 16 or above 512, wide
+    nets of more than 8 classes; bf16 nets past k_mlpw's LDS.
+  * Dm4 % 16 != 0 cannot occur (Dm4 is Dm rounded up to 16 where the problem is created).
+  * 48 states of 100 offspring on 256 CUs run 960 workgroups of 5 rows (1,200 of 4 on 304).
+"""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+EXPECTED = """\
+mlp botnet 312-64-64-32-2              kind=6 rw=1 no=2 xml=0 cj=0 bf=0 direct=0 co=0 maxct=0
+mlp botnet 312-64-64-32-3              kind=6 rw=1 no=8 xml=0 cj=0 bf=0 direct=0 co=0 maxct=0
+mlp botnet 432-64-64-32-2              kind=6 rw=1 no=2 xml=0 cj=0 bf=0 direct=0 co=0 maxct=0
+mlp botnet odd Dm 431-64-32-2          kind=1 rw=0 no=0 xml=0 cj=1 bf=0 direct=1 co=0 maxct=0
+mlp lcld 64-32-2 (ML rows)             kind=7 rw=1 no=2 xml=1 cj=0 bf=0 direct=0 co=0 maxct=0
+mlp lcld 64-32-3 (ML rows)             kind=7 rw=1 no=8 xml=1 cj=0 bf=0 direct=0 co=0 maxct=0
+mlp botnet hidden 80 (genes, even Dm)  kind=1 rw=0 no=0 xml=0 cj=2 bf=0 direct=1 co=1 maxct=0
+mlp botnet hidden 128 (genes)          kind=1 rw=0 no=0 xml=0 cj=2 bf=0 direct=1 co=1 maxct=0
+mlp botnet hidden 80 (genes, odd Dm)   kind=1 rw=0 no=0 xml=0 cj=2 bf=0 direct=1 co=0 maxct=0
+mlp lcld hidden 80 (ML rows)           kind=2 rw=0 no=0 xml=0 cj=2 bf=0 direct=0 co=0 maxct=0
+mlp lcld hidden 128 (ML rows)          kind=2 rw=0 no=0 xml=0 cj=2 bf=0 direct=0 co=0 maxct=0
+mlp bf16 hidden 64                     kind=1 rw=0 no=0 xml=0 cj=1 bf=1 direct=1 co=0 maxct=0
+mlp bf16 hidden 128                    kind=1 rw=0 no=0 xml=0 cj=2 bf=1 direct=1 co=0 maxct=0
+mlp bf16 hidden 256                    kind=4 rw=0 no=0 xml=0 cj=2 bf=0 direct=0 co=0 maxct=0
+mlp bf16 hidden 512                    kind=4 rw=0 no=0 xml=0 cj=4 bf=0 direct=0 co=0 maxct=0
+mlp fp32 hidden 144                    kind=5 rw=0 no=0 xml=0 cj=2 bf=0 direct=0 co=0 maxct=0
+mlp fp32 hidden 256                    kind=5 rw=0 no=0 xml=0 cj=2 bf=0 direct=0 co=0 maxct=0
+mlp fp32 hidden 512                    kind=5 rw=0 no=0 xml=0 cj=4 bf=0 direct=0 co=0 maxct=0
+mlp fp32 512 wide, 8 classes, Dm4 432  kind=5 rw=0 no=0 xml=0 cj=4 bf=0 direct=0 co=0 maxct=0
+mlp fp32 hidden 512, Dm4 624           kind=5 rw=0 no=0 xml=0 cj=4 bf=0 direct=0 co=0 maxct=0
+mlp fp32 hidden 512, Dm4 640           kind=0 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=8
+mlp bf16 hidden 512, Dm4 640           kind=0 rw=0 no=0 xml=0 cj=0 bf=1 direct=0 co=0 maxct=8
+mlp fp32 hidden 520 (not 16 k)         kind=0 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=8
+mlp fp32 hidden 200 (not 16 k)         kind=0 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=4
+mlp fp32 hidden 528 (> 512)            kind=0 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=8
+mlp fp32 9 classes, hidden 256         kind=0 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=4
+mlp fp32 9 classes, hidden 64          kind=1 rw=0 no=0 xml=0 cj=1 bf=0 direct=1 co=1 maxct=0
+mlp one Dense layer                    kind=1 rw=0 no=0 xml=0 cj=1 bf=0 direct=1 co=1 maxct=0
+mlp no model                           kind=-1 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=0
+mlp MV_MLPR=0 botnet 312-64-64-32-2    kind=1 rw=0 no=0 xml=0 cj=1 bf=0 direct=1 co=1 maxct=0
+mlp MV_MLPR=0 lcld 64-32-2             kind=2 rw=0 no=0 xml=0 cj=1 bf=0 direct=0 co=0 maxct=0
+mlp MV_MLPR_RW=2 botnet 312-64-64-32-2 kind=6 rw=2 no=2 xml=0 cj=0 bf=0 direct=0 co=0 maxct=0
+mlp MV_MLPR_RW=2 botnet ... 3 classes  kind=6 rw=2 no=8 xml=0 cj=0 bf=0 direct=0 co=0 maxct=0
+mlp MV_MLPR_RW=2 lcld 64-32-2          kind=7 rw=1 no=2 xml=1 cj=0 bf=0 direct=0 co=0 maxct=0
+mlp MV_MLPR_RW=7 botnet 312-64-64-32-2 kind=6 rw=2 no=2 xml=0 cj=0 bf=0 direct=0 co=0 maxct=0
+mlp MV_MLP_V1 botnet hidden 128        kind=5 rw=0 no=0 xml=0 cj=1 bf=0 direct=0 co=0 maxct=0
+mlp MV_MLP_V1 botnet 312-64-64-32-2    kind=6 rw=1 no=2 xml=0 cj=0 bf=0 direct=0 co=0 maxct=0
+mlp MV_MLP_V1 bf16 hidden 128          kind=4 rw=0 no=0 xml=0 cj=1 bf=0 direct=0 co=0 maxct=0
+mlp MV_MLPW bf16 hidden 64             kind=4 rw=0 no=0 xml=0 cj=1 bf=0 direct=0 co=0 maxct=0
+mlp MV_MLPW fp32 hidden 128            kind=1 rw=0 no=0 xml=0 cj=2 bf=0 direct=1 co=1 maxct=0
+mlp MV_MLPW_OFF bf16 hidden 256        kind=0 rw=0 no=0 xml=0 cj=0 bf=1 direct=0 co=0 maxct=4
+mlp MV_MLPW_OFF bf16 hidden 64         kind=1 rw=0 no=0 xml=0 cj=1 bf=1 direct=1 co=0 maxct=0
+mlp MV_MLPW32=0 fp32 hidden 144        kind=0 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=4
+mlp MV_MLPW32=0 fp32 hidden 512        kind=0 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=8
+mlp MV_MLP_CO=0 botnet hidden 80       kind=1 rw=0 no=0 xml=0 cj=2 bf=0 direct=1 co=0 maxct=0
+row botnet full layout V 432           kind=2 nt=7 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0
+row botnet compact V 312 Vr 432        kind=2 nt=5 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0
+row botnet SBX                         kind=2 nt=7 ident=1 sbx=1 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0
+row botnet slim 0                      kind=2 nt=7 ident=1 sbx=0 slim=0 cons=0 nv=0 full=0 need_plan=1 plan_missing=0
+row botnet slim 0 SBX                  kind=2 nt=7 ident=1 sbx=1 slim=0 cons=0 nv=0 full=0 need_plan=1 plan_missing=0
+row botnet mode 0 (genes given)        kind=2 nt=7 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=0 plan_missing=0
+row botnet mode 1 without a plan       kind=2 nt=7 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=1
+row botnet do_eval 0                   kind=0 nt=8 ident=1 sbx=0 slim=0 cons=0 nv=0 full=0 need_plan=0 plan_missing=0
+row lcld V 8                           kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=8 full=1 need_plan=0 plan_missing=0
+row lcld V 9                           kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=16 full=1 need_plan=0 plan_missing=0
+row lcld V 15                          kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=16 full=1 need_plan=0 plan_missing=0
+row lcld V 16                          kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=16 full=1 need_plan=0 plan_missing=0
+row lcld V 17                          kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=32 full=1 need_plan=0 plan_missing=0
+row lcld V 32                          kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=32 full=1 need_plan=0 plan_missing=0
+row lcld V 33                          kind=0 nt=1 ident=0 sbx=0 slim=0 cons=2 nv=0 full=0 need_plan=0 plan_missing=0
+row lcld V 15 without financial ops    kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=16 full=0 need_plan=0 plan_missing=0
+row lcld SBX                           kind=0 nt=1 ident=0 sbx=1 slim=0 cons=2 nv=0 full=0 need_plan=0 plan_missing=0
+row lcld SBX, mode 0                   kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=16 full=1 need_plan=0 plan_missing=0
+row lcld expr columns (full_ops 2)     kind=0 nt=1 ident=0 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0
+row botnet expr columns (full_ops 2)   kind=0 nt=8 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0
+row lcld compact                       kind=0 nt=1 ident=0 sbx=0 slim=0 cons=2 nv=0 full=0 need_plan=0 plan_missing=0
+row lcld with a sum-diff op            kind=0 nt=1 ident=0 sbx=0 slim=0 cons=2 nv=0 full=0 need_plan=0 plan_missing=0
+row lcld 65 ops                        kind=0 nt=1 ident=0 sbx=0 slim=0 cons=2 nv=0 full=0 need_plan=0 plan_missing=0
+row lcld do_eval 0                     kind=0 nt=1 ident=0 sbx=0 slim=0 cons=0 nv=0 full=0 need_plan=0 plan_missing=0
+row ident max(V, Dm4) 128              kind=0 nt=2 ident=1 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0
+row ident max(V, Dm4) 129              kind=2 nt=4 ident=1 sbx=0 slim=0 cons=0 nv=0 full=0 need_plan=1 plan_missing=0
+row ident V 120 (Dm4 128)              kind=0 nt=2 ident=1 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0
+row ident V 40 (one gene per lane)     kind=0 nt=1 ident=1 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0
+row ident V 100 (two per lane)         kind=0 nt=2 ident=1 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0
+row ident V 257 (k_genc NT 5)          kind=2 nt=5 ident=1 sbx=0 slim=0 cons=0 nv=0 full=0 need_plan=1 plan_missing=0
+row ident V 384 (k_genc NT 6)          kind=2 nt=6 ident=1 sbx=0 slim=0 cons=0 nv=0 full=0 need_plan=1 plan_missing=0
+row ident V 512 (k_genc NT 8)          kind=2 nt=8 ident=1 sbx=0 slim=0 cons=0 nv=0 full=0 need_plan=1 plan_missing=0
+row ident V 513 (k_genc NT 16)         kind=2 nt=16 ident=1 sbx=0 slim=0 cons=0 nv=0 full=0 need_plan=1 plan_missing=0
+row not ident V 432                    kind=0 nt=8 ident=0 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0
+row not ident V 600                    kind=0 nt=16 ident=0 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0
+row MV_NARROW=0 lcld V 15              kind=0 nt=1 ident=0 sbx=0 slim=0 cons=2 nv=0 full=0 need_plan=0 plan_missing=0
+row MV_NARROW=0 botnet                 kind=2 nt=7 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0
+row MV_GENC=0 botnet                   kind=0 nt=8 ident=1 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0
+row MV_GENC=0 botnet SBX               kind=0 nt=8 ident=1 sbx=1 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0
+row MV_GENC=0 lcld V 15                kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=16 full=1 need_plan=0 plan_missing=0
+rows_per_wg n 100, 387 states          rows=20 chunks_per_state=5 workgroups=1935
+rows_per_wg n 203, 387 states          rows=23 chunks_per_state=9 workgroups=3483
+rows_per_wg n 100, 48 states           rows=5 chunks_per_state=20 workgroups=960
+rows_per_wg n 100, 12 states           rows=4 chunks_per_state=25 workgroups=300
+rows_per_wg n 100, 1 state             rows=4 chunks_per_state=25 workgroups=25
+rows_per_wg n 3, 387 states            rows=3 chunks_per_state=1 workgroups=387
+rows_per_wg n 3, 1 state               rows=3 chunks_per_state=1 workgroups=1
+rows_per_wg n 100, states unknown      rows=20 chunks_per_state=5 workgroups=5
+rows_per_wg n 100, 48 states, 304 CUs  rows=4 chunks_per_state=25 workgroups=1200
+rows_per_wg n 100, 48 states, cap 16   rows=15 chunks_per_state=7 workgroups=336
+rows_per_wg n 100, 387 states, cap 64  rows=25 chunks_per_state=4 workgroups=1548
+rows_per_wg n 100, 387 states, cap 1   rows=4 chunks_per_state=25 workgroups=9675
+"""
+
+
+def test_route_table(tmp_path):
+    cxx = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(cxx):
+        pytest.skip("hipcc not found")
+    here = os.path.dirname(os.path.abspath(__file__))
+    csrc = os.path.join(os.path.dirname(here), "moeva2-ijcai22-replication_amd", "csrc")
+    exe = str(tmp_path / "routes_check")
+    subprocess.run([cxx, "-O2", "-std=c++17", "-I", csrc,
+                    os.path.join(here, "native", "routes_check.cpp"), "-o", exe],
+                   check=True, capture_output=True, timeout=300)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr
+    got, want = r.stdout.splitlines(), EXPECTED.splitlines()
+    diff = [f"- {w}\n+ {g}" for w, g in zip(want, got) if w != g]
+    assert not diff and len(got) == len(want), "\n".join(diff) or (len(got), len(want))
