@@ -59,10 +59,11 @@ enum {
   MV_OP_TF_RATIO_ALPHA_ZERO = 14, /* isnan(x[a0]-x[a1]) ? 0 : x[a0]/(x[a1]+k0)   botnet:250-269 */
   MV_OP_TF_ABS_SUMDIFF_OFF = 15,  /* |sum(pool[a0:a1]) - sum(pool[a1:a2])| - k0  botnet:55-75 */
   /* user-defined column (engine extension; no reference counterpart): a postfix expression
-   * over the row, interpreted on the device in fp64.  op_arg = (a0 offset of its first word in
-   * expr_code, a1 word count, a2 maximum stack depth, 0).  mv_engine_create simulates every
-   * such column and refuses a malformed one (MV_ERR_ARG), so the device only ever interprets
-   * checked code. */
+   * over the row, interpreted on the device in fp64 (mv_engine_*) or, as a tensor-path column
+   * of mv_pgd_*, in fp32 together with its reverse-mode derivative.  op_arg = (a0 offset of its
+   * first word in expr_code, a1 word count, a2 maximum stack depth, 0).  mv_engine_create and
+   * mv_pgd_create simulate every such column and refuse a malformed one (MV_ERR_ARG), so the
+   * device only ever interprets checked code. */
   MV_OP_EXPR = 16,
 };
 
@@ -85,8 +86,9 @@ enum {
   MV_X_ISNAN = 25, MV_X_ISINF = 26,
   MV_X_WHERE = 27, /* pops b, a, c; pushes c != 0 ? a : b */
 };
-/* Limits of one MV_OP_EXPR column. */
-enum { MV_EXPR_MAX_DEPTH = 8, MV_EXPR_MAX_WORDS = 256 };
+/* Limits of one MV_OP_EXPR column.  MV_EXPR_MAX_TAPE (mv_pgd_create only): instructions per
+ * column; every instruction's value is kept on a tape for the reverse sweep. */
+enum { MV_EXPR_MAX_DEPTH = 8, MV_EXPR_MAX_WORDS = 256, MV_EXPR_MAX_TAPE = 64 };
 
 typedef struct mv_problem_desc {
   int32_t D;                  /* ML feature count */
@@ -374,14 +376,18 @@ int mv_det_pow(int64_t n, const double* x, const double* y, double* out);
 
 /* ---- C-PGD: the constrained gradient attack (src/attacks/pgd/atk.py:74-163 on ART's PGD
  * loop, src/attacks/pgd/classifier.py:107-332 loss_gradient), whole loop on device.  All
- * device buffers are fp32; rows are ML-scaled (scaler.transform(x)) unless stated. */
+ * device buffers are fp32; rows are ML-scaled (scaler.transform(x)) unless stated.
+ * An MV_OP_EXPR column is evaluated in fp32 on XF(f) = (x[f] - min[f]) / scale[f] with the value
+ * semantics of the MV_X_* table (POW is powf) and differentiated by a reverse sweep with
+ * autograd's rules; the comparisons, AND OR XOR NOT ISNAN ISINF and the
+ * condition of WHERE pass no gradient to their operands. */
 typedef struct mv_pgd_desc {
   int32_t D;                  /* ML feature count (== model dims[0]) */
   const double* ml_scale;     /* host [D] ML MinMaxScaler scale_ (cast to fp32) */
   const double* ml_min;       /* host [D] min_ */
   const int32_t* mutable_mask;/* host [D] 1 = mutable */
   int32_t C;                  /* tensor program: constraint columns */
-  const int32_t* op_code;     /* host [C] MV_OP_* (tensor-path subset) */
+  const int32_t* op_code;     /* host [C] MV_OP_* (tensor-path subset, MV_OP_EXPR included) */
   const int32_t* op_arg;      /* host [C*4] */
   const double* op_karg;      /* host [C*2] */
   int32_t n_pool;
@@ -392,6 +398,12 @@ typedef struct mv_pgd_desc {
   int32_t repair_install[4];  /* repair: amount, term, rate, installment features of the LCLD
                                  formula; repair_install[0] < 0: no formula repair */
   double tol;                 /* 1e-3 */
+  /* MV_OP_EXPR bytecode, as in mv_problem_desc (appended: a zero-initialised tail describes a
+   * program without EXPR columns).  Constants are rounded to fp32 once at create time. */
+  int32_t n_expr_code;
+  const int32_t* expr_code;   /* host [n_expr_code] */
+  int32_t n_expr_const;
+  const double* expr_const;   /* host [n_expr_const] */
 } mv_pgd_desc;
 
 /* loss_flags: which terms the gradient is taken of. */

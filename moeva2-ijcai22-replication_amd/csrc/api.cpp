@@ -503,7 +503,23 @@ static int build_problem(const HostProblem& h, const HostModel* hm, const std::v
 // each column's op_arg becomes (pool offset of its first word, word count, pool offset of
 // the constant table, depth): the kernels reach both through the pool tables they already
 // stage, and a program without EXPR columns keeps its tables to the byte.
-static int expr_check(const mv_problem_desc* pd) {
+//
+// The check takes raw tables, so mv_engine_create and mv_pgd_create share it; max_tape > 0
+// (mv_pgd_create) also bounds a column's instruction count, which is its tape length in
+// k_pgd (pgd_expr.h).
+struct ExprTables {
+  int C, D;
+  const int32_t* op_code;
+  const int32_t* op_arg;
+  int n_pool;
+  const int32_t* idx_pool;
+  int n_expr_code;
+  const int32_t* expr_code;
+  int n_expr_const;
+  const double* expr_const;
+  int max_tape;
+};
+static int expr_check(const ExprTables* pd) {
   const int C = pd->C, D = pd->D, n_pool = pd->n_pool;
   bool any = false;
   for (int c = 0; c < C; ++c) any |= pd->op_code[c] == MV_OP_EXPR;
@@ -523,9 +539,10 @@ static int expr_check(const mv_problem_desc* pd) {
     if (off < 0 || off > nw - n) return bad(c, "code range outside expr_code");
     if (dmax < 1 || dmax > MV_EXPR_MAX_DEPTH) return bad(c, "stack depth outside 1..MV_EXPR_MAX_DEPTH");
     const int32_t* w = pd->expr_code + off;
-    int depth = 0, pc = 0;
+    int depth = 0, pc = 0, n_ins = 0;
     while (pc < n) {
       const int op = w[pc++];
+      ++n_ins;
       int pops = 0, operands = 0;
       if (op == MV_X_FEAT || op == MV_X_CONST) operands = 1;
       else if (op == MV_X_SUMF) operands = 2;
@@ -548,8 +565,68 @@ static int expr_check(const mv_problem_desc* pd) {
       if (depth > dmax) return bad(c, "stack deeper than the column declares");
     }
     if (depth != 1) return bad(c, "the column does not end with exactly one value");
+    if (pd->max_tape > 0 && n_ins > pd->max_tape)
+      return bad(c, "more than MV_EXPR_MAX_TAPE instructions");
   }
   return MV_OK;
+}
+static int expr_check(const mv_problem_desc* pd) {
+  const ExprTables t = {pd->C, pd->D, pd->op_code, pd->op_arg, pd->n_pool, pd->idx_pool,
+                        pd->n_expr_code, pd->expr_code, pd->n_expr_const, pd->expr_const, 0};
+  return expr_check(&t);
+}
+
+// mv_pgd_create: the checked EXPR columns decoded for k_pgd (pgd_expr.h): one int4 per
+// instruction -- opcode, operands, and the links of the reverse sweep (the ordinal of the
+// instruction that produced the left operand, for WHERE also the condition's; the first
+// ordinal of the instruction's subtree; bit 24 on the instructions autograd does not
+// differentiate through: comparisons, AND OR XOR NOT ISNAN ISINF and the root of a WHERE
+// condition).  op_arg (a copy) gets (first instruction, instruction count, 0, 0) per EXPR
+// column.  Returns the largest instruction count.
+static_assert(MV_EXPR_MAX_TAPE <= 256, "ordinals are packed in 8 bits");
+static int expr_decode(const mv_pgd_desc* d, std::vector<int32_t>& op_arg,
+                       std::vector<int32_t>& ins) {
+  int tape = 0;
+  for (int c = 0; c < d->C; ++c) {
+    if (d->op_code[c] != MV_OP_EXPR) continue;
+    const int32_t* w = d->expr_code + op_arg[(size_t)c * 4];
+    const int n = op_arg[(size_t)c * 4 + 1];
+    const int first = (int)ins.size() / 4;
+    int ord[MV_EXPR_MAX_DEPTH + 1], start[MV_EXPR_MAX_DEPTH + 1], depth = 0, i = 0;
+    for (int pc = 0; pc < n; ++i) {
+      const int op = w[pc++];
+      int a0 = 0, a1 = 0, la = 0, lc = 0, st = i, skip = 0;
+      if (op <= MV_X_SUMF) {
+        a0 = w[pc++];
+        if (op == MV_X_SUMF) a1 = w[pc++];
+      } else if (op <= MV_X_XOR) {
+        depth -= 2;
+        la = ord[depth];
+        st = start[depth];
+        skip = op >= MV_X_LT;
+      } else if (op <= MV_X_ISINF) {
+        depth -= 1;
+        st = start[depth];
+        skip = op >= MV_X_NOT;
+      } else {  // WHERE: c a b
+        depth -= 3;
+        lc = ord[depth];
+        la = ord[depth + 1];
+        st = start[depth];
+        ins[(size_t)(first + lc) * 4 + 3] |= 1 << 24;
+      }
+      ord[depth] = i;
+      start[depth] = st;
+      ++depth;
+      const int32_t e[4] = {op, a0, a1, la | (lc << 8) | (st << 16) | (skip << 24)};
+      ins.insert(ins.end(), e, e + 4);
+    }
+    op_arg[(size_t)c * 4] = first;
+    op_arg[(size_t)c * 4 + 1] = i;
+    op_arg[(size_t)c * 4 + 2] = op_arg[(size_t)c * 4 + 3] = 0;
+    tape = i > tape ? i : tape;
+  }
+  return tape;
 }
 static void expr_append(const mv_problem_desc* pd, HostProblem& h) {
   const int C = pd->C, nw = pd->n_expr_code, nk = pd->n_expr_const;
@@ -1820,12 +1897,13 @@ int mv_debug_checks(int32_t* record, int32_t* compiled) {
   if (!record) return fail(MV_ERR_ARG, "null record");
   if (compiled) *compiled = MV_CHECKS_ON;
   HIPCHK(hipDeviceSynchronize());
-  int ev[8], sv[8];
+  int ev[8], sv[8], pg[8];
   HIPCHK(take_checks_eval(ev));
   HIPCHK(take_checks_survive(sv));
-  const int* r = ev[0] ? ev : sv;
+  HIPCHK(take_checks_pgd(pg));
+  const int* r = ev[0] ? ev : (sv[0] ? sv : pg);
   for (int k = 0; k < 8; ++k) record[k] = r[k];
-  record[5] = ev[5] + sv[5];
+  record[5] = ev[5] + sv[5] + pg[5];
   return MV_OK;
 }
 
@@ -1991,6 +2069,7 @@ int mv_pgd_create(int32_t device, const mv_pgd_desc* d, const mv_model_desc* md,
       case MV_OP_ABS_RATIO: case MV_OP_MONTHDIFF: case MV_OP_TF_RATIO_ALPHA_NEG: nfeat = 3; break;
       case MV_OP_TF_INSTALL_MIN: nfeat = 4; break;
       case MV_OP_ABS_SUMDIFF: case MV_OP_TF_ABS_SUMDIFF_OFF: pooled = true; break;
+      case MV_OP_EXPR: break;  // checked as a whole below
       default:
         return fail(MV_ERR_ARG, "mv_pgd_create: op " + std::to_string(code) +
                                     " has no tensor-path form");
@@ -2000,6 +2079,14 @@ int mv_pgd_create(int32_t device, const mv_pgd_desc* d, const mv_model_desc* md,
     if (pooled && !(0 <= ar[0] && ar[0] <= ar[1] && ar[1] <= ar[2] && ar[2] <= d->n_pool))
       return fail(MV_ERR_ARG, "mv_pgd_create: pool range out of bounds");
   }
+  {
+    const ExprTables t = {d->C, d->D, d->op_code, d->op_arg, d->n_pool, d->idx_pool,
+                          d->n_expr_code, d->expr_code, d->n_expr_const, d->expr_const,
+                          MV_EXPR_MAX_TAPE};
+    if (const int rc = expr_check(&t)) return rc;
+  }
+  std::vector<int32_t> op_arg(d->op_arg, d->op_arg + (size_t)d->C * 4), xins;
+  const int tape = expr_decode(d, op_arg, xins);
   if (d->n_ohe > 0) {
     if (!d->ohe_offsets || !d->ohe_feats || d->ohe_offsets[0] != 0)
       return fail(MV_ERR_ARG, "mv_pgd_create: bad one-hot groups");
@@ -2023,6 +2110,7 @@ int mv_pgd_create(int32_t device, const mv_pgd_desc* d, const mv_model_desc* md,
   for (int l = 0; l <= md->n_layers; ++l) a.dims[l] = md->dims[l];
   a.Dp = d->D | 1;
   a.tol = (float)d->tol;
+  a.tape = tape;
   a.n_ohe = d->n_ohe;
   for (int k = 0; k < 4; ++k) a.inst[k] = d->repair_install[0] >= 0 ? d->repair_install[k] : -1;
   // LDS plan: stage the first layer when the weights and one wave's tiles fit
@@ -2056,7 +2144,13 @@ int mv_pgd_create(int32_t device, const mv_pgd_desc* d, const mv_model_desc* md,
   K((float**)&a.mask, mk.data(), mk.size());
   K((float**)&a.op_k, ok.data(), ok.size());
   K((int**)&a.op_code, d->C ? d->op_code : &zero, d->C ? (size_t)d->C : 1);
-  K((int**)&a.op_arg, d->C ? d->op_arg : &zero, d->C ? (size_t)d->C * 4 : 1);
+  K((int**)&a.op_arg, d->C ? op_arg.data() : &zero, d->C ? (size_t)d->C * 4 : 1);
+  if (tape > 0) {  // constants rounded to fp32 once, here
+    std::vector<float> xk((size_t)d->n_expr_const + 1, 0.f);
+    for (int i = 0; i < d->n_expr_const; ++i) xk[i] = (float)d->expr_const[i];
+    K((int32_t**)&a.xins, xins.data(), xins.size());
+    K((float**)&a.xk, xk.data(), xk.size());
+  }
   K((int**)&a.pool, d->n_pool ? d->idx_pool : &zero, d->n_pool ? (size_t)d->n_pool : 1);
   K((int**)&a.ohe_off, d->n_ohe ? d->ohe_offsets : &zero, (size_t)d->n_ohe + (d->n_ohe ? 1 : 1));
   K((int**)&a.ohe_feat, d->n_ohe ? d->ohe_feats : &zero,

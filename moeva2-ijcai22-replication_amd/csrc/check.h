@@ -46,6 +46,8 @@ enum : int {
   CK_SURV_DUP = 26,     // k_survive: the survivors are not n_out distinct individuals
                         // (value = gen * 4096 + state in its group, bound = free count);
                         // the first such state's inputs go to the survival dump
+  CK_PGD_TAPE = 27,     // k_pgd / k_pgd_grad: EXPR tape slot (an instruction's ordinal or an
+                        // operand link) outside [0, tape)
 };
 // survival dump (checks builds): [0] 1 = valid, [1] gen, [2] state in its group, [3] N,
 // [4, 7) carried ideal, [7, 10) carried worst, [10, 19) carried extremes, [19] has_extreme,
@@ -106,6 +108,7 @@ __device__ __forceinline__ T* chk_ptr(T* p, const T* lo, const T* hi, int code) 
 
 hipError_t take_checks_eval(int* out);
 hipError_t take_checks_survive(int* out);
+hipError_t take_checks_pgd(int* out);
 hipError_t take_survival_dump(double* out);  // [SURV_DUMP_N], cleared
 
 }  // namespace mv

@@ -47,6 +47,13 @@ struct PgdArgs {
   float eta_tab[PGD_ETA_TAB];
   float* grad;                     // k_pgd_grad: [n][D] raw gradient
   float* losses;                   // k_pgd_grad: [n][2 + C]
+  // MV_OP_EXPR columns (pgd_expr.h); a program without one leaves these zero and runs the
+  // kernels without the interpreter
+  const int4* xins;                // decoded instructions of all EXPR columns; an EXPR column's
+                                   // op_arg = (first instruction, instruction count, 0, 0)
+  const float* xk;                 // their constants, rounded to fp32 once on the host
+  int tape;                        // largest column's instruction count (0: no EXPR column):
+                                   // the per-wave tape is [tape][PGD_ROWS] floats of LDS
 };
 
 size_t pgd_lds_bytes(const PgdArgs& a);

@@ -13,10 +13,15 @@
 //
 // fp32 throughout, built with -ffp-contract=off: the per-row arithmetic is the order written
 // in DESIGN.md section 7a, which tests/pgd_torch_ref.py restates.
+//
+// k_pgd<true> / k_pgd_grad<true> are the instances for a tensor program with MV_OP_EXPR
+// columns (pgd_expr.h: an fp32 interpreter with a value tape in LDS and a reverse sweep); a
+// program without one runs the <false> instances, which hold no interpreter code.
 #include <hip/hip_runtime.h>
 
 #include "../../include/moeva_mi355x.h"
 #include "pgd.h"
+#include "pgd_expr.h"
 #include "wave.h"
 
 namespace mv {
@@ -33,7 +38,8 @@ struct PgdTile {
   float* dz[2];                   // [16][hmax + 1]
   float* dl;                      // [16][PGD_MAX_OUT] d loss / d logit
   float* lossc;                   // [16] cross-entropy
-  int* ys;                        // [16] labels
+  int* ys;                        // [16] labels; EXPR instances: then the value tape
+                                  // [a.tape][16] of one EXPR column (pgd_tape)
   const float* W[PGD_MAX_LAYERS]; // LDS (staged) or global
   int ldw[PGD_MAX_LAYERS];
 };
@@ -242,8 +248,10 @@ __device__ __forceinline__ float installment(float x0, float r, float t, float* 
 // active column (c_j - tol > 0).  Kinks follow TF: abs'(0) = 0, relu'(0) = 0, floor' = 0,
 // floormod' = 1, minimum gives the gradient to the smaller argument (the first on a tie).
 // cols (or nullptr): global row of 2 + C losses, columns written at cols[2 + j].
+// EXPR: the program may hold MV_OP_EXPR columns; tp is the lane's tape column.
+template <bool EXPR>
 __device__ __forceinline__ float constraint_sweep(const PgdArgs& a, const float* xr, float* gr,
-                                                  bool back, float* cols) {
+                                                  bool back, float* cols, float* tp) {
   const float* __restrict__ sc = a.scale;
   const float* __restrict__ mn = a.minv;
 #define XF(f) ((xr[(f)] - mn[(f)]) / sc[(f)])
@@ -254,6 +262,16 @@ __device__ __forceinline__ float constraint_sweep(const PgdArgs& a, const float*
     const int a0 = a.op_arg[4 * j], a1 = a.op_arg[4 * j + 1], a2 = a.op_arg[4 * j + 2],
               a3 = a.op_arg[4 * j + 3];
     const float k0 = a.op_k[2 * j];
+    if (EXPR && code == MV_OP_EXPR) {  // a0: first instruction, a1: instruction count
+      const int4* ins = a.xins + a0;
+      const float ct = expr_forward(a, ins, a1, xr, tp) - a.tol;
+      const bool active = ct > 0.f;
+      const float v = active ? ct : (ct != ct ? ct : 0.f);
+      if (cols) cols[2 + j] = v;
+      sum = sum + v;
+      if (back && active) expr_reverse(a, ins, a1, gr, tp);
+      continue;
+    }
     float c = 0.f;
     // up to 4 (feature, d c / d xf) pairs; pooled ops sweep their pool instead
     int gf[4] = {0, 0, 0, 0};
@@ -459,8 +477,13 @@ __device__ __forceinline__ void pgd_step(const PgdArgs& a, const PgdTile& t, int
   }
 }
 
+// The wave's EXPR value tape: the last part of its LDS slice (no PgdTile member, so the
+// instances without EXPR columns keep their frame).
+__device__ __forceinline__ float* pgd_tape(const PgdTile& t) { return (float*)t.ys + PGD_ROWS; }
+
 // Gradient of the selected loss wrt the scaled rows into t.gs; returns (lanes 0..15) the
 // constraint sum.  cols: this lane's global losses row or nullptr.
+template <bool EXPR>
 __device__ __forceinline__ float pgd_gradient(const PgdArgs& a, const PgdTile& t, int lane,
                                               bool want_class, float* cols) {
   const bool flip = (a.loss_flags & PGD_LOSS_FLIP) != 0;
@@ -479,13 +502,15 @@ __device__ __forceinline__ float pgd_gradient(const PgdArgs& a, const PgdTile& t
   float sum = 0.f;
   if (cons || cols) {
     if (lane < PGD_ROWS)
-      sum = constraint_sweep(a, t.xs + lane * a.Dp, t.gs + lane * a.Dp, cons, cols);
+      sum = constraint_sweep<EXPR>(a, t.xs + lane * a.Dp, t.gs + lane * a.Dp, cons, cols,
+                                   EXPR ? pgd_tape(t) + lane : nullptr);
     wave_sync();
   }
   return sum;
 }
 
 // Carve the dynamic LDS block: weights first (shared by the workgroup), then the waves' tiles.
+template <bool EXPR>
 __device__ __forceinline__ void pgd_setup(const PgdArgs& a, float* smem, PgdTile& t) {
   float* p = smem;
   for (int l = 0; l < a.n_layers; ++l) {
@@ -505,6 +530,7 @@ __device__ __forceinline__ void pgd_setup(const PgdArgs& a, float* smem, PgdTile
   const int hm1 = pgd_hmax(a) + 1;
   size_t per = (size_t)2 * PGD_ROWS * a.Dp + 2 * PGD_ROWS * hm1 + PGD_ROWS * PGD_MAX_OUT + 2 * PGD_ROWS;
   for (int l = 1; l < a.n_layers; ++l) per += (size_t)PGD_ROWS * (a.dims[l] + 1);
+  if (EXPR) per += (size_t)PGD_ROWS * a.tape;
   p += per * (threadIdx.x >> 6);
   t.xs = p; p += PGD_ROWS * a.Dp;
   t.gs = p; p += PGD_ROWS * a.Dp;
@@ -518,6 +544,7 @@ __device__ __forceinline__ void pgd_setup(const PgdArgs& a, float* smem, PgdTile
   t.lossc = p; p += PGD_ROWS;
   t.ys = (int*)p;
 }
+
 
 // rows row0 .. row0 + 15 of x_in into t.xs (rows past n: zeros), labels into t.ys
 __device__ __forceinline__ void pgd_load(const PgdArgs& a, const PgdTile& t, int lane, int row0) {
@@ -539,10 +566,11 @@ __device__ __forceinline__ void pgd_load(const PgdArgs& a, const PgdTile& t, int
 
 }  // namespace
 
+template <bool EXPR>
 __global__ __launch_bounds__(64 * PGD_MAX_WAVES) void k_pgd(const PgdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float pgd_smem[];
   PgdTile t;
-  pgd_setup(a, pgd_smem, t);
+  pgd_setup<EXPR>(a, pgd_smem, t);
   const int lane = threadIdx.x & 63;
   const int row0 = (blockIdx.x * a.wpb + (threadIdx.x >> 6)) * PGD_ROWS;
   if (row0 >= a.n) return;
@@ -552,7 +580,7 @@ __global__ __launch_bounds__(64 * PGD_MAX_WAVES) void k_pgd(const PgdArgs a) {
     last_layer(a, t, lane, true);
   }
   for (int it = 0; it < a.max_iter; ++it) {
-    pgd_gradient(a, t, lane, false, nullptr);
+    pgd_gradient<EXPR>(a, t, lane, false, nullptr);
     float eta = a.eps_step;
     if (a.adaptive) {
       int p = it / a.iter_per_step;
@@ -570,10 +598,11 @@ __global__ __launch_bounds__(64 * PGD_MAX_WAVES) void k_pgd(const PgdArgs a) {
 
 // One gradient evaluation: grad [n][D] (raw: before mask and normalisation), losses
 // [n][2 + C] = (loss_class, constraint sum, the C columns).
+template <bool EXPR>
 __global__ __launch_bounds__(64 * PGD_MAX_WAVES) void k_pgd_grad(const PgdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float pgd_smem[];
   PgdTile t;
-  pgd_setup(a, pgd_smem, t);
+  pgd_setup<EXPR>(a, pgd_smem, t);
   const int lane = threadIdx.x & 63;
   const int row0 = (blockIdx.x * a.wpb + (threadIdx.x >> 6)) * PGD_ROWS;
   if (row0 >= a.n) return;
@@ -581,7 +610,7 @@ __global__ __launch_bounds__(64 * PGD_MAX_WAVES) void k_pgd_grad(const PgdArgs a
   float* cols = nullptr;
   if (lane < PGD_ROWS && row0 + lane < a.n && a.losses)
     cols = a.losses + (size_t)(row0 + lane) * (2 + a.C);
-  const float sum = pgd_gradient(a, t, lane, true, cols);
+  const float sum = pgd_gradient<EXPR>(a, t, lane, true, cols);
   if (cols) {
     cols[0] = t.lossc[lane];
     cols[1] = sum;
@@ -606,6 +635,7 @@ static size_t pgd_wave_floats(const PgdArgs& a) {
   size_t per = (size_t)2 * PGD_ROWS * a.Dp + 2 * PGD_ROWS * (hm + 1) + PGD_ROWS * PGD_MAX_OUT +
                2 * PGD_ROWS;
   for (int l = 1; l < a.n_layers; ++l) per += (size_t)PGD_ROWS * (a.dims[l] + 1);
+  per += (size_t)PGD_ROWS * a.tape;  // the EXPR value tape (0 without an EXPR column)
   return per;
 }
 
@@ -648,10 +678,14 @@ static hipError_t pgd_launch(Kern kern, PgdArgs a, hipStream_t stream) {
   return hipGetLastError();
 }
 
-hipError_t launch_pgd(const PgdArgs& a, hipStream_t stream) { return pgd_launch(k_pgd, a, stream); }
+// a.tape > 0: the program has an EXPR column (mv_pgd_create) and runs the <true> instances
+hipError_t launch_pgd(const PgdArgs& a, hipStream_t stream) {
+  return a.tape > 0 ? pgd_launch(k_pgd<true>, a, stream) : pgd_launch(k_pgd<false>, a, stream);
+}
 
 hipError_t launch_pgd_grad(const PgdArgs& a, hipStream_t stream) {
-  return pgd_launch(k_pgd_grad, a, stream);
+  return a.tape > 0 ? pgd_launch(k_pgd_grad<true>, a, stream)
+                    : pgd_launch(k_pgd_grad<false>, a, stream);
 }
 
 hipError_t launch_pgd_repair(const PgdArgs& a, float* x, hipStream_t stream) {
@@ -659,5 +693,7 @@ hipError_t launch_pgd_repair(const PgdArgs& a, float* x, hipStream_t stream) {
   hipLaunchKernelGGL(k_pgd_repair, dim3((a.n + 127) / 128), dim3(128), 0, stream, a, x);
   return hipGetLastError();
 }
+
+MV_DEFINE_TAKE_CHECKS(take_checks_pgd)
 
 }  // namespace mv

@@ -80,7 +80,9 @@ class PgdDesc(C.Structure):
                 ("mutable_mask", _i32p), ("C", C.c_int32), ("op_code", _i32p), ("op_arg", _i32p),
                 ("op_karg", _f64p), ("n_pool", C.c_int32), ("idx_pool", _i32p),
                 ("n_ohe", C.c_int32), ("ohe_offsets", _i32p), ("ohe_feats", _i32p),
-                ("repair_install", C.c_int32 * 4), ("tol", C.c_double)]
+                ("repair_install", C.c_int32 * 4), ("tol", C.c_double),
+                ("n_expr_code", C.c_int32), ("expr_code", _i32p),
+                ("n_expr_const", C.c_int32), ("expr_const", _f64p)]
 
 
 class PgdParams(C.Structure):
@@ -643,6 +645,11 @@ class Pgd:
         ri = list(repair_install) if repair_install is not None else [-1, -1, -1, -1]
         d.repair_install = (C.c_int32 * 4)(*[int(v) for v in ri])
         d.tol = float(tol)
+        xc, xk = program.expr_arrays()  # both empty without an EXPR column
+        d.n_expr_code = int(xc.shape[0])
+        d.expr_code = P(xc if xc.size else np.zeros(1), np.int32, C.c_int32)
+        d.n_expr_const = int(xk.shape[0])
+        d.expr_const = P(xk if xk.size else np.zeros(1), np.float64, C.c_double)
         md = _model_desc(weights, biases, keep)
         self._h = C.c_void_p()
         check(lib().mv_pgd_create(device, C.byref(d), C.byref(md), C.byref(self._h)))

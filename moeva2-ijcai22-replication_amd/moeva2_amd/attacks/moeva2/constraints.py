@@ -44,11 +44,15 @@ class ConstraintProgram:
         self.pool.extend(int(v) for v in second)
         self.add(op, (o0, o1, len(self.pool)), k)
 
-    def add_expr(self, node, n_features: int = None):
+    def add_expr(self, node, n_features: int = None, max_tape: int = None):
         """Append a user-defined column (MV_OP_EXPR): ``node`` is an expression of
         ``moeva2_amd.attacks.moeva2.expr``, compiled here; its constants and ``sum_of`` index
-        lists join the program's tables.  op_arg = (code offset, word count, stack depth, 0)."""
+        lists join the program's tables.  op_arg = (code offset, word count, stack depth, 0).
+        ``max_tape``: the instruction limit of a tensor-path column (``expr.MAX_TAPE``)."""
         code, consts, pool = _expr.compile_expr(node, n_features)
+        if max_tape is not None and _expr.tape_length(code) > max_tape:
+            raise ValueError(f"expression has {_expr.tape_length(code)} instructions (limit "
+                             f"{max_tape} for a tensor-path column)")
         kmap = []  # the column's constants in the program's table (one entry per bit pattern)
         for v in consts:
             bits = float(v).hex()
@@ -128,7 +132,7 @@ class Constraints(abc.ABC, metaclass=abc.ABCMeta):
         as a device program (engine extension)."""
         raise NotImplementedError(
             f"{type(self).__name__} has no tensor-path constraint program (C-PGD covers the "
-            "LCLD and botnet classes)")
+            "LCLD and botnet classes and ExprConstraints)")
 
     def check_constraints_error(self, x: np.ndarray):
         """constraints.py:73-77."""
@@ -316,18 +320,42 @@ class ExprConstraints(TabularConstraints):
     """Constraints given as expressions (``moeva2_amd.attacks.moeva2.expr``): one expression
     per column over the ML-space row, compiled to MV_OP_EXPR columns, so a new dataset's
     constraints run on the device without a dedicated op code.  ``evaluate_numpy`` states
-    the same columns on the CPU."""
+    the same columns on the CPU.
 
-    def __init__(self, feature_path: str, constraints_path: str, expressions):
+    The same expressions are the tensor path (``evaluate(x, use_tensors=True)``, the C-PGD
+    constraint loss: fp32 on the device, differentiated there), unless ``tensor_expressions``
+    gives one smoothed variant per column, as the reference's ``evaluate_tf2`` does (alpha in
+    a denominator that can be 0, a hinge in place of a difference).
+    ``expr.evaluate_grad_numpy`` states their values and gradient on the CPU."""
+
+    def __init__(self, feature_path: str, constraints_path: str, expressions,
+                 tensor_expressions=None):
         super().__init__(feature_path, constraints_path)
         self.expressions = list(expressions)
+        self.tensor_expressions = None if tensor_expressions is None else list(tensor_expressions)
+        if (self.tensor_expressions is not None
+                and len(self.tensor_expressions) != len(self.expressions)):
+            raise ValueError(f"{len(self.tensor_expressions)} tensor expressions for "
+                             f"{len(self.expressions)} expressions")
         self.device_program()  # compile now: a bad expression fails here, not in the attack
+        if self.tensor_expressions is not None:
+            self.tensor_program()
 
     def device_program(self) -> ConstraintProgram:
         prog = ConstraintProgram()
         D = int(self._feature_type.shape[0])
         for e in self.expressions:
             prog.add_expr(e, D)
+        return prog
+
+    def tensor_program(self) -> ConstraintProgram:
+        """EXPR columns of ``tensor_expressions`` (default: of ``expressions``); a column
+        longer than ``expr.MAX_TAPE`` instructions raises ValueError."""
+        exprs = self.expressions if self.tensor_expressions is None else self.tensor_expressions
+        prog = ConstraintProgram()
+        D = int(self._feature_type.shape[0])
+        for e in exprs:
+            prog.add_expr(e, D, max_tape=_expr.MAX_TAPE)
         return prog
 
     def get_nb_constraints(self) -> int:

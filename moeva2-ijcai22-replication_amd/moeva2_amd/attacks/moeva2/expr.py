@@ -25,6 +25,12 @@ Instruction set (int32 words, postfix, operands inline; left operand emitted fir
 
 Limits (the device's, checked again by ``mv_engine_create``): operand stack depth
 ``MAX_DEPTH`` = 8, ``MAX_WORDS`` = 256 code words per column.
+
+C-PGD runs the same bytecode as a tensor-path column (``ExprConstraints.tensor_program``): the
+device interprets it in fp32 and differentiates it with a reverse sweep over a tape of every
+instruction's value, so a tensor-path column has at most ``MAX_TAPE`` = 64 instructions
+(checked again by ``mv_pgd_create``).  ``evaluate_grad_numpy`` states that computation on the
+CPU: the derivative rules, autograd's with TF's kinks, are listed there.
 """
 from __future__ import annotations
 
@@ -35,6 +41,7 @@ import numpy as np
 
 MAX_DEPTH = 8
 MAX_WORDS = 256
+MAX_TAPE = 64
 
 OPCODES = dict(X=1, K=2, SUMF=3, ADD=4, SUB=5, MUL=6, DIV=7, MIN=8, MAX=9, MOD=10, POW=11,
                LT=12, LE=13, GT=14, GE=15, EQ=16, NE=17, AND=18, OR=19, XOR=20,
@@ -301,3 +308,181 @@ def evaluate_numpy(exprs, x, tol: float = 1e-3, pow_fn=np.power) -> np.ndarray:
         if tol is not None:
             out[out <= tol] = 0.0
     return out
+
+
+def decode(code: Sequence[int]):
+    """Compiled code words -> one tuple per instruction ``(op, a0, a1, left, cond, start,
+    skip)``, the table ``mv_pgd_create`` builds for the reverse sweep: ``left`` is the ordinal
+    (index in this list) of the instruction that produced the left operand (``a`` of a binary
+    operator and of WHERE; the right operand is always the previous instruction), ``cond``
+    the one that produced WHERE's condition, ``start`` the first ordinal of the instruction's
+    subtree, and ``skip`` marks the instructions no gradient passes through: comparisons,
+    AND OR XOR NOT ISNAN ISINF and the root of a WHERE condition."""
+    code = [int(w) for w in code]
+    out, stack, pc = [], [], 0
+    while pc < len(code):
+        op, i = code[pc], len(out)
+        pc += 1
+        a0 = a1 = left = cond = 0
+        start, skip = i, False
+        if op <= OPCODES["SUMF"]:
+            a0 = code[pc]
+            a1 = code[pc + 1] if op == OPCODES["SUMF"] else 0
+            pc += N_OPERANDS[op]
+        elif op <= OPCODES["XOR"]:
+            stack.pop()
+            left, start = stack.pop()
+            skip = op >= OPCODES["LT"]
+        elif op <= OPCODES["ISINF"]:
+            start = stack.pop()[1]
+            skip = op >= OPCODES["NOT"]
+        else:
+            stack.pop()
+            left = stack.pop()[0]
+            cond, start = stack.pop()
+            out[cond] = out[cond][:6] + (True,)
+        stack.append((i, start))
+        out.append((op, a0, a1, left, cond, start, skip))
+    return out
+
+
+def tape_length(code: Sequence[int]) -> int:
+    """Instructions of compiled code words: the column's tape length in C-PGD."""
+    return len(decode(code))
+
+
+def evaluate_grad_numpy(exprs, x, tol: float = 1e-3, dtype=np.float64, pow_fn=np.power):
+    """What C-PGD computes of the columns ``exprs`` on the rows ``x`` (n, D), in ``dtype``:
+    ``(cols (n, C), grad (n, D))`` with ``cols = max(c - tol, 0)`` (NaN stays NaN) and
+    ``grad = d(sum of cols) / dx``.
+
+    The device's operations in the device's order: every column's bytecode forward with each
+    instruction's value kept on a tape; then, on the rows where ``c - tol > 0``, the
+    instructions backwards with an adjoint stack that starts from 1 -- an operator pops its
+    adjoint ``g``, reads its operands ``a, b`` from the tape and pushes their adjoints, a leaf
+    ``X f`` adds ``g`` to ``grad[:, f]`` (``sum_of``: to every listed feature, in order), a
+    constant drops it.  Columns in ascending order, all into one gradient row.  Rules:
+
+        a + b: g, g      a - b: g, -g      a * b: g b, g a      a / b: g / b, -(g a) / (b b)
+        minimum: all of g to b if b < a else to a (the first on a tie); maximum: b > a
+        mod(a, b): g, -g floor(a / b)      power(a, b): g (b a^(b-1)), g (a^b log a), the
+        latter 0 where a == 0 and b >= 0   -a: -g      absolute: g sgn(a), sgn(0) = 0
+        floor: 0      where(c, a, b): g to a where c != 0, else to b
+
+    A zero adjoint is propagated arithmetically, as autograd does, so ``where(b != 0, a / b,
+    0)`` has a NaN derivative for ``a`` at ``b = 0``; write the smoothed ``a / (b + alpha)``
+    as the reference's tensor paths do.  Comparisons, ``& | ^ ~``, ``isnan``, ``isinf`` and
+    the condition of ``where`` are outside the differentiated graph: nothing below them is
+    visited.  ``pow_fn`` stands in for the device's ``powf``.  No GPU, no torch."""
+    dt = np.dtype(dtype).type
+    x = np.atleast_2d(np.asarray(x, dt))
+    n, D = x.shape
+    cols = np.empty((n, len(exprs)), dt)
+    grad = np.zeros((n, D), dt)
+    one, zero = dt(1), dt(0)
+    O = OPCODES
+
+    def flag(mask):
+        return np.where(mask, one, zero)
+
+    def sgn(a):
+        return np.where(a > 0, one, np.where(a < 0, -one, zero))
+
+    with np.errstate(all="ignore"):
+        for c, e in enumerate(exprs):
+            if e is None:
+                raise ValueError("empty expression")
+            code, consts, pool = compile_expr(e, D)
+            ins = decode(code)
+            if len(ins) > MAX_TAPE:
+                raise ValueError(f"column {c} has {len(ins)} instructions (limit {MAX_TAPE})")
+            consts = consts.astype(dt)
+            tape, st = [], []
+            for op, a0, a1, _l, _c, _s, _k in ins:
+                if op == O["X"]:
+                    v = x[:, a0]
+                elif op == O["K"]:
+                    v = np.full(n, consts[a0], dt)
+                elif op == O["SUMF"]:
+                    v = np.zeros(n, dt)
+                    for f in pool[a0:a1]:
+                        v = v + x[:, f]
+                elif op <= O["XOR"]:
+                    b = st.pop()
+                    a = st.pop()
+                    if op == O["ADD"]: v = a + b
+                    elif op == O["SUB"]: v = a - b
+                    elif op == O["MUL"]: v = a * b
+                    elif op == O["DIV"]: v = a / b
+                    elif op == O["MIN"]: v = np.where((a < b) | (a != a), a, b)
+                    elif op == O["MAX"]: v = np.where((a > b) | (a != a), a, b)
+                    elif op == O["MOD"]: v = np.mod(a, b)
+                    elif op == O["POW"]: v = np.asarray(pow_fn(a, b), dt)
+                    elif op == O["LT"]: v = flag(a < b)
+                    elif op == O["LE"]: v = flag(a <= b)
+                    elif op == O["GT"]: v = flag(a > b)
+                    elif op == O["GE"]: v = flag(a >= b)
+                    elif op == O["EQ"]: v = flag(a == b)
+                    elif op == O["NE"]: v = flag(a != b)
+                    elif op == O["AND"]: v = flag((a != 0) & (b != 0))
+                    elif op == O["OR"]: v = flag((a != 0) | (b != 0))
+                    else: v = flag((a != 0) ^ (b != 0))
+                elif op <= O["ISINF"]:
+                    a = st.pop()
+                    if op == O["NEG"]: v = -a
+                    elif op == O["ABS"]: v = np.absolute(a)
+                    elif op == O["FLOOR"]: v = np.floor(a)
+                    elif op == O["NOT"]: v = flag(a == 0)
+                    elif op == O["ISNAN"]: v = flag(a != a)
+                    else: v = flag(np.isinf(a))
+                else:
+                    b = st.pop()
+                    a = st.pop()
+                    cnd = st.pop()
+                    v = np.where(cnd != 0, a, b)
+                v = np.asarray(v, dt)
+                st.append(v)
+                tape.append(v)
+            ct = st[0] - dt(tol)
+            active = ct > 0
+            cols[:, c] = np.where(active, ct, np.where(ct != ct, ct, zero))
+            gs = [np.full(n, one, dt)]
+            i = len(ins) - 1
+            while i >= 0:
+                op, a0, a1, left, cond, start, skip = ins[i]
+                g = gs.pop()
+                if skip:
+                    i = start - 1
+                    continue
+                if op == O["X"]:
+                    grad[:, a0] = grad[:, a0] + np.where(active, g, zero)
+                elif op == O["SUMF"]:
+                    for f in pool[a0:a1]:
+                        grad[:, f] = grad[:, f] + np.where(active, g, zero)
+                elif op == O["K"]:
+                    pass
+                elif op <= O["POW"]:
+                    a, b = tape[left], tape[i - 1]
+                    if op == O["ADD"]: ga, gb = g, g
+                    elif op == O["SUB"]: ga, gb = g, -g
+                    elif op == O["MUL"]: ga, gb = g * b, g * a
+                    elif op == O["DIV"]: ga, gb = g / b, -(g * a) / (b * b)
+                    elif op == O["MIN"]: ga, gb = np.where(b < a, zero, g), np.where(b < a, g, zero)
+                    elif op == O["MAX"]: ga, gb = np.where(b > a, zero, g), np.where(b > a, g, zero)
+                    elif op == O["MOD"]: ga, gb = g, -g * np.floor(a / b)
+                    else:
+                        ga = g * (b * np.asarray(pow_fn(a, b - one), dt))
+                        gb = np.where((a == 0) & (b >= 0), zero, g * (tape[i] * np.log(a)))
+                    gs.append(np.asarray(ga, dt))
+                    gs.append(np.asarray(gb, dt))
+                elif op <= O["FLOOR"]:
+                    a = tape[i - 1]
+                    gs.append(-g if op == O["NEG"] else
+                              (g * sgn(a) if op == O["ABS"] else np.zeros(n, dt)))
+                else:
+                    cnd = tape[cond]
+                    gs.append(np.zeros(n, dt))
+                    gs.append(np.where(cnd != 0, g, zero))
+                    gs.append(np.where(cnd != 0, zero, g))
+                i -= 1
+    return cols, grad
