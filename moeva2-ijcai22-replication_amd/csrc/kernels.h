@@ -119,8 +119,12 @@ __host__ __device__ inline VaryOff vary_offsets(const DProblem& p) {
   o.x0 = take(Dm4 * 8);
   o.sb = kb(off);
   o.rb = (unsigned)(((size_t)p.D * 8 + 15) & ~(size_t)15);
-  // whole 64-gene registers: k_genc writes every lane of its row registers unconditionally
-  o.rbs = (unsigned)(((size_t)p.Dm + 63) / 64 * 64 * 8);
+  // whole 64-gene registers: k_genc writes every lane of its NT row registers unconditionally,
+  // and genc_nt is 4 below 193 genes and 16 above 512 -- more registers than ceil(Dm / 64)
+  // there (sized by Dm alone, a wave's padding lanes wrote into the next wave's row: V 129,
+  // 143, 160 and 513 evaluated other rows' operands; botnet's 432 / 312 genes fill 7 / 5)
+  const size_t regs = ((size_t)p.Dm + 63) / 64, nt = (size_t)genc_nt(p);
+  o.rbs = (unsigned)((regs > nt ? regs : nt) * 64 * 8);
   return o;
 }
 // k_gen LDS: region B [, C, E] [, X + one row per wave for one-hot decoding]

@@ -162,7 +162,7 @@ inline int vary_nt(const DProblem& p) {
 }
 // k_genc's genes per lane: the exact ceil(max(V, Dm4) / 64) from 4 to 8 (every unused
 // register slot costs a masked instruction per row in every phase), else 16.
-inline int genc_nt(const DProblem& p) {
+__host__ __device__ inline int genc_nt(const DProblem& p) {
   const int m = p.V > p.Dm4 ? p.V : p.Dm4;
   const int nt = (m + 63) / 64;
   return nt <= 4 ? 4 : nt <= 8 ? nt : 16;

@@ -89,6 +89,72 @@ static void chunk(const char* name, int n, int states, int cus, int cap) {
               per * (states > 0 ? states : 1));
 }
 
+// The synthetic shapes of tests/synth_problem.py (one line per GPU case of
+// tests/test_gpu_row_routes.py; "/sbx": the case's second run): the attack's problem as
+// build_problem derives it -- stored genes V of Vr, Dm, C, ident, full_ops, n_sumdiff, slim --
+// under a D-32-16-2 classifier.  The line names the shape, then gives the row route and the
+// classifier kind, so the instance a GPU case claims to reach is pinned here.
+struct Synth {
+  const char* name;
+  int V, Vr, Dm, C, ident, full_ops, n_sd, slim, sbx;
+};
+static const Synth kSynth[] = {
+    {"n8p", 8, 8, 8, 5, 1, 0, 0, 0, 0},
+    {"n8p/sbx", 8, 8, 8, 5, 1, 0, 0, 0, 1},
+    {"n8f", 8, 8, 13, 8, 0, 1, 0, 0, 0},
+    {"n9", 9, 9, 9, 6, 1, 0, 0, 0, 0},
+    {"n16f", 16, 16, 19, 10, 0, 1, 0, 0, 0},
+    {"n17f", 17, 17, 22, 10, 0, 1, 0, 0, 0},
+    {"n32", 32, 32, 64, 64, 0, 0, 0, 0, 0},
+    {"n32d", 32, 32, 65, 64, 0, 0, 0, 0, 0},
+    {"n32c", 32, 32, 64, 65, 0, 0, 0, 0, 0},
+    {"n8s", 8, 8, 8, 6, 1, 0, 1, 0, 0},
+    {"n2", 2, 2, 2, 2, 1, 0, 0, 1, 0},
+    {"g33", 33, 33, 33, 20, 1, 0, 0, 0, 0},
+    {"g33/sbx", 33, 33, 33, 20, 1, 0, 0, 0, 1},
+    {"g64", 64, 64, 64, 40, 1, 0, 0, 0, 0},
+    {"g65", 65, 65, 65, 40, 1, 0, 0, 0, 0},
+    {"g65/sbx", 65, 65, 65, 40, 1, 0, 0, 0, 1},
+    {"g128", 128, 128, 128, 70, 1, 0, 0, 0, 0},
+    {"o40f", 40, 40, 51, 24, 0, 1, 0, 0, 0},
+    {"o100p", 100, 100, 150, 70, 0, 0, 0, 0, 0},
+    {"o100p/sbx", 100, 100, 150, 70, 0, 0, 0, 0, 1},
+    {"o300f", 300, 300, 330, 100, 0, 1, 0, 0, 0},
+    {"o520p", 520, 520, 600, 150, 0, 0, 0, 0, 0},
+    {"c129", 129, 129, 129, 70, 1, 0, 0, 1, 0},
+    {"c129/sbx", 129, 129, 129, 70, 1, 0, 0, 1, 1},
+    {"c256", 256, 256, 256, 100, 1, 0, 0, 1, 0},
+    {"c257", 257, 257, 257, 100, 1, 0, 0, 1, 0},
+    {"c384", 384, 384, 384, 130, 1, 0, 0, 1, 0},
+    {"c384/sbx", 384, 384, 384, 130, 1, 0, 0, 1, 1},
+    {"c385", 385, 385, 385, 130, 1, 0, 0, 1, 0},
+    {"c512", 512, 512, 512, 150, 1, 0, 0, 1, 0},
+    {"c513", 513, 513, 513, 150, 1, 0, 0, 1, 0},
+    {"c1024", 1024, 1024, 1024, 300, 1, 0, 0, 1, 0},
+    {"c300x", 300, 300, 300, 400, 1, 0, 0, 0, 0},
+    {"c300d", 300, 300, 300, 100, 1, 0, 3, 1, 0},
+    {"k_slab", 136, 200, 136, 80, 1, 0, 0, 1, 0},
+    {"k_last", 199, 200, 199, 80, 1, 0, 0, 1, 0},
+    {"k_odd", 143, 200, 143, 80, 1, 0, 0, 1, 0},
+    {"k_few", 3, 200, 3, 80, 1, 0, 0, 1, 0},
+    {"k_mixed", 160, 200, 160, 80, 1, 0, 0, 1, 0},
+};
+static void synth(const Synth& s) {
+  DProblem p = problem(2048, s.V, s.Dm, s.C, s.ident != 0, s.full_ops, {32, 16, 2});
+  p.Vr = s.Vr;
+  p.compact = s.V < s.Vr;
+  p.n_sumdiff = s.n_sd;
+  p.slim = s.slim;
+  char name[96];
+  std::snprintf(name, sizeof name, "synth %s V%d Dm4 %d C%d i%d f%d sd%d c%d s%d x%d", s.name,
+                p.V, p.Dm4, p.C, s.ident, s.full_ops, s.n_sd, (int)p.compact, s.slim, s.sbx);
+  const RowRoute r = row_route(rows(p, 1, s.sbx), Switches{});
+  std::printf("row %-34s kind=%d nt=%d ident=%d sbx=%d slim=%d cons=%d nv=%d full=%d "
+              "need_plan=%d plan_missing=%d mlp=%d\n", name, r.kind, r.nt, (int)r.ident,
+              (int)r.sbx, (int)r.slim, r.cons, r.nv, (int)r.full, (int)r.need_plan,
+              (int)r.plan_missing, mlp_route(p, Switches{}).kind);
+}
+
 int main() {
   // --- classifier routes, default switches
   mlp("botnet 312-64-64-32-2", botnet({64, 64, 32, 2}, 312));
@@ -224,5 +290,8 @@ int main() {
   chunk("n 100, 48 states, cap 16", 100, 48, 256, 16);
   chunk("n 100, 387 states, cap 64", 100, 387, 256, 64);
   chunk("n 100, 387 states, cap 1", 100, 387, 256, 1);
+
+  // --- the synthetic shapes of the GPU row-route cases
+  for (const Synth& s : kSynth) synth(s);
   return 0;
 }

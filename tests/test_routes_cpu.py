@@ -18,6 +18,13 @@ What the table shows beyond the routes the GPU tests run:
     nets of more than 8 classes; bf16 nets past k_mlpw's LDS.
   * Dm4 % 16 != 0 cannot occur (Dm4 is Dm rounded up to 16 where the problem is created).
   * 48 states of 100 offspring on 256 CUs run 960 workgroups of 5 rows (1,200 of 4 on 304).
+
+The "row synth" lines are the synthetic shapes of tests/synth_problem.py, one per GPU case of
+tests/test_gpu_row_routes.py ("/sbx": the case's second run).  The name gives the attack's
+problem -- stored genes V, Dm4, C, i(dent), f(ull_ops), sd = ABS_SUMDIFF columns, c(ompact),
+s(lim), x = SBX -- and mlp= the classifier kind under the cases' D-32-16-2 net: they pin the
+NT / NV / FULL / SLIM instance the kind reported on the GPU does not show
+(tests/test_synth_problem_cpu.py checks each line against the shape the builder makes).
 """
 import os
 import shutil
@@ -123,6 +130,45 @@ rows_per_wg n 100, 48 states, 304 CUs  rows=4 chunks_per_state=25 workgroups=120
 rows_per_wg n 100, 48 states, cap 16   rows=15 chunks_per_state=7 workgroups=336
 rows_per_wg n 100, 387 states, cap 64  rows=25 chunks_per_state=4 workgroups=1548
 rows_per_wg n 100, 387 states, cap 1   rows=4 chunks_per_state=25 workgroups=9675
+row synth n8p V8 Dm4 16 C5 i1 f0 sd0 c0 s0 x0 kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=8 full=0 need_plan=0 plan_missing=0 mlp=6
+row synth n8p/sbx V8 Dm4 16 C5 i1 f0 sd0 c0 s0 x1 kind=0 nt=1 ident=1 sbx=1 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=6
+row synth n8f V8 Dm4 16 C8 i0 f1 sd0 c0 s0 x0 kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=8 full=1 need_plan=0 plan_missing=0 mlp=7
+row synth n9 V9 Dm4 16 C6 i1 f0 sd0 c0 s0 x0 kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=16 full=0 need_plan=0 plan_missing=0 mlp=1
+row synth n16f V16 Dm4 32 C10 i0 f1 sd0 c0 s0 x0 kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=16 full=1 need_plan=0 plan_missing=0 mlp=7
+row synth n17f V17 Dm4 32 C10 i0 f1 sd0 c0 s0 x0 kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=32 full=1 need_plan=0 plan_missing=0 mlp=7
+row synth n32 V32 Dm4 64 C64 i0 f0 sd0 c0 s0 x0 kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=32 full=0 need_plan=0 plan_missing=0 mlp=7
+row synth n32d V32 Dm4 80 C64 i0 f0 sd0 c0 s0 x0 kind=0 nt=2 ident=0 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=7
+row synth n32c V32 Dm4 64 C65 i0 f0 sd0 c0 s0 x0 kind=0 nt=1 ident=0 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=7
+row synth n8s V8 Dm4 16 C6 i1 f0 sd1 c0 s0 x0 kind=0 nt=1 ident=1 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=6
+row synth n2 V2 Dm4 16 C2 i1 f0 sd0 c0 s1 x0 kind=1 nt=0 ident=0 sbx=0 slim=0 cons=0 nv=8 full=0 need_plan=0 plan_missing=0 mlp=6
+row synth g33 V33 Dm4 48 C20 i1 f0 sd0 c0 s0 x0 kind=0 nt=1 ident=1 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=1
+row synth g33/sbx V33 Dm4 48 C20 i1 f0 sd0 c0 s0 x1 kind=0 nt=1 ident=1 sbx=1 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=1
+row synth g64 V64 Dm4 64 C40 i1 f0 sd0 c0 s0 x0 kind=0 nt=1 ident=1 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=6
+row synth g65 V65 Dm4 80 C40 i1 f0 sd0 c0 s0 x0 kind=0 nt=2 ident=1 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=1
+row synth g65/sbx V65 Dm4 80 C40 i1 f0 sd0 c0 s0 x1 kind=0 nt=2 ident=1 sbx=1 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=1
+row synth g128 V128 Dm4 128 C70 i1 f0 sd0 c0 s0 x0 kind=0 nt=2 ident=1 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=6
+row synth o40f V40 Dm4 64 C24 i0 f1 sd0 c0 s0 x0 kind=0 nt=1 ident=0 sbx=0 slim=0 cons=2 nv=0 full=0 need_plan=0 plan_missing=0 mlp=7
+row synth o100p V100 Dm4 160 C70 i0 f0 sd0 c0 s0 x0 kind=0 nt=4 ident=0 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=7
+row synth o100p/sbx V100 Dm4 160 C70 i0 f0 sd0 c0 s0 x1 kind=0 nt=4 ident=0 sbx=1 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=7
+row synth o300f V300 Dm4 336 C100 i0 f1 sd0 c0 s0 x0 kind=0 nt=8 ident=0 sbx=0 slim=0 cons=2 nv=0 full=0 need_plan=0 plan_missing=0 mlp=7
+row synth o520p V520 Dm4 608 C150 i0 f0 sd0 c0 s0 x0 kind=0 nt=16 ident=0 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=7
+row synth c129 V129 Dm4 144 C70 i1 f0 sd0 c0 s1 x0 kind=2 nt=4 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=1
+row synth c129/sbx V129 Dm4 144 C70 i1 f0 sd0 c0 s1 x1 kind=2 nt=4 ident=1 sbx=1 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=1
+row synth c256 V256 Dm4 256 C100 i1 f0 sd0 c0 s1 x0 kind=2 nt=4 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=6
+row synth c257 V257 Dm4 272 C100 i1 f0 sd0 c0 s1 x0 kind=2 nt=5 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=1
+row synth c384 V384 Dm4 384 C130 i1 f0 sd0 c0 s1 x0 kind=2 nt=6 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=6
+row synth c384/sbx V384 Dm4 384 C130 i1 f0 sd0 c0 s1 x1 kind=2 nt=6 ident=1 sbx=1 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=6
+row synth c385 V385 Dm4 400 C130 i1 f0 sd0 c0 s1 x0 kind=2 nt=7 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=1
+row synth c512 V512 Dm4 512 C150 i1 f0 sd0 c0 s1 x0 kind=2 nt=8 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=6
+row synth c513 V513 Dm4 528 C150 i1 f0 sd0 c0 s1 x0 kind=2 nt=16 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=1
+row synth c1024 V1024 Dm4 1024 C300 i1 f0 sd0 c0 s1 x0 kind=2 nt=16 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=6
+row synth c300x V300 Dm4 304 C400 i1 f0 sd0 c0 s0 x0 kind=2 nt=5 ident=1 sbx=0 slim=0 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=6
+row synth c300d V300 Dm4 304 C100 i1 f0 sd3 c0 s1 x0 kind=2 nt=5 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=6
+row synth k_slab V136 Dm4 144 C80 i1 f0 sd0 c1 s1 x0 kind=2 nt=4 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=6
+row synth k_last V199 Dm4 208 C80 i1 f0 sd0 c1 s1 x0 kind=2 nt=4 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=1
+row synth k_odd V143 Dm4 144 C80 i1 f0 sd0 c1 s1 x0 kind=2 nt=4 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=1
+row synth k_few V3 Dm4 16 C80 i1 f0 sd0 c1 s1 x0 kind=0 nt=1 ident=1 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=1
+row synth k_mixed V160 Dm4 160 C80 i1 f0 sd0 c1 s1 x0 kind=2 nt=4 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=6
 """
 
 
