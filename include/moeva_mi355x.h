@@ -436,6 +436,56 @@ int mv_pgd_run(mv_pgd* p, const mv_pgd_params* params, int32_t n, const float* x
 /* Constraints.fix_features_types on feature-space (unscaled) rows, in place: dev [n][D]. */
 int mv_pgd_repair(mv_pgd* p, int32_t n, float* x_feature_space, void* stream);
 
+/* ---- Training the Dense MLP (adversarial retraining: train_model of the reference's
+ * src/experiments/lcld/model.py:9-42, Keras Adam on the mean sparse cross-entropy), fp32.
+ * Parameter layout of every flat [n_params] array (gradient, Adam m and v): per layer, W
+ * row-major (in, out) followed by b.  A step is two launches (the batch's per-workgroup
+ * gradients, then their fixed-order sum and the update); no atomics, so a result depends
+ * on its inputs alone. */
+typedef struct mv_train_opt {
+  double lr;       /* Adam, Keras form: w -= lr_t m / (sqrt(v) + epsilon), */
+  double beta1;    /* lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t)          */
+  double beta2;
+  double epsilon;
+} mv_train_opt;
+
+typedef struct mv_train mv_train;
+/* The model limits are mv_pgd_create's (2..6 layers, hidden widths multiples of 16 up to 512,
+ * 1..8 outputs, one tile's activations within LDS).  The initial weights are copied from
+ * `model`; m, v and the step count start at 0. */
+int mv_train_create(int32_t device, const mv_model_desc* model, const mv_train_opt* opt,
+                    mv_train** out);
+void mv_train_destroy(mv_train* t);
+/* n_steps consecutive optimiser steps.  x_scaled dev [n][D], y dev [n] int32 class indices,
+ * perm dev [n] int32 or NULL (identity).  Step s takes the rows at positions first_row +
+ * s * batch ... of the permuted order, at most batch of them and none past n (a short last
+ * batch divides by its own size); every step must hold a row.  step_losses dev [n_steps]
+ * (each step's mean cross-entropy, before its update) or NULL. */
+int mv_train_steps(mv_train* t, int32_t n, const float* x_scaled, const int32_t* y,
+                   const int32_t* perm, int32_t first_row, int32_t batch, int32_t n_steps,
+                   float* step_losses, void* stream);
+/* Forward only over n rows: loss_and_correct dev [2] = (mean cross-entropy, rows whose
+ * argmax -- the first maximum -- equals y, as a float: exact up to 2^24 rows). */
+int mv_train_eval(mv_train* t, int32_t n, const float* x_scaled, const int32_t* y,
+                  float* loss_and_correct, void* stream);
+/* The reduced gradient of the mean cross-entropy over all n rows (one batch), no update:
+ * grad dev [n_params], loss dev [1] (may be NULL). */
+int mv_train_grad(mv_train* t, int32_t n, const float* x_scaled, const int32_t* y,
+                  const int32_t* perm, float* grad, float* loss, void* stream);
+/* Copies to host arrays (synchronise the stream of the last call first): W[l] [dims[l] x
+ * dims[l+1]], b[l] [dims[l+1]]; m, v [n_params] (either may be NULL) and the step count. */
+int mv_train_get(mv_train* t, float* const* W, float* const* b);
+int mv_train_get_state(mv_train* t, float* m, float* v, int64_t* step);
+/* Replace m, v (host [n_params]) and the step count: resuming, and the tests' way to a late
+ * step. */
+int mv_train_set_state(mv_train* t, const float* m, const float* v, int64_t step);
+/* Profiling (tools/train_speed.py): with on != 0, mv_train_steps brackets each of its two
+ * launches with HIP events and waits for every step; the call clears the sums, which
+ * mv_train_get_kernel_times returns: device ms in k_train_grad and k_train_adam over `steps`
+ * optimiser steps. */
+int mv_train_set_profiling(mv_train* t, int32_t on);
+int mv_train_get_kernel_times(mv_train* t, double* grad_ms, double* adam_ms, int64_t* steps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@
 #include "kernels.h"
 #include "pgd.h"
 #include "rowops.h"
+#include "train.h"
 
 using namespace mv;
 
@@ -2226,6 +2227,243 @@ int mv_pgd_repair(mv_pgd* p, int32_t n, float* x, void* stream) {
   PgdArgs a = p->a;
   a.n = n;
   HIPCHK(launch_pgd_repair(a, x, (hipStream_t)stream));
+  return MV_OK;
+}
+
+// ---- training (train.hip)
+struct mv_train {
+  int device = 0;
+  TrainArgs a{};
+  mv_train_opt opt{};
+  int64_t step = 0;
+  bool profiling = false;  // mv_train_set_profiling: HIP events around each launch
+  double grad_ms = 0.0, adam_ms = 0.0;
+  int64_t timed_steps = 0;
+  float *params = nullptr, *m = nullptr, *v = nullptr, *partial = nullptr,
+        *loss_partial = nullptr, *scalars = nullptr;  // scalars: [2] loss / correct scratch
+  ~mv_train() {
+    (void)hipSetDevice(device);
+    for (float* x : {params, m, v, partial, loss_partial, scalars}) (void)hipFree(x);
+  }
+};
+
+int mv_train_create(int32_t device, const mv_model_desc* md, const mv_train_opt* opt,
+                    mv_train** out) {
+  if (!md || !opt || !out) return fail(MV_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (md->n_layers < 2 || md->n_layers > PGD_MAX_LAYERS)
+    return fail(MV_ERR_ARG, "mv_train_create: 2..6 layers");
+  if (md->dims[0] < 1) return fail(MV_ERR_ARG, "mv_train_create: input width < 1");
+  for (int l = 1; l < md->n_layers; ++l)
+    if (md->dims[l] % 16 != 0 || md->dims[l] < 16 || md->dims[l] > 512)
+      return fail(MV_ERR_ARG, "mv_train_create: hidden widths must be multiples of 16 and <= 512");
+  if (md->dims[md->n_layers] < 1 || md->dims[md->n_layers] > PGD_MAX_OUT)
+    return fail(MV_ERR_ARG, "mv_train_create: output width must be 1..8");
+  if (!(opt->lr > 0.0) || !(opt->beta1 >= 0.0 && opt->beta1 < 1.0) ||
+      !(opt->beta2 >= 0.0 && opt->beta2 < 1.0) || !(opt->epsilon >= 0.0))
+    return fail(MV_ERR_ARG, "mv_train_create: lr > 0, beta1 and beta2 in [0, 1), epsilon >= 0");
+  mv_train* t = new mv_train();
+  t->device = device;
+  t->opt = *opt;
+  TrainArgs& a = t->a;
+  a.D = md->dims[0];
+  a.Dp = a.D | 1;
+  a.n_layers = md->n_layers;
+  size_t np = 0;
+  for (int l = 0; l <= md->n_layers; ++l) a.dims[l] = md->dims[l];
+  for (int l = 0; l < md->n_layers; ++l) {
+    a.off_w[l] = (int)np;
+    np += (size_t)a.dims[l] * a.dims[l + 1];
+    a.off_b[l] = (int)np;
+    np += (size_t)a.dims[l + 1];
+  }
+  a.n_params = (int)np;
+  if (train_plan_model(a) != hipSuccess) {
+    delete t;
+    return fail(MV_ERR_ARG, "mv_train_create: one tile's activations do not fit in LDS");
+  }
+  std::vector<float> flat(np);
+  for (int l = 0; l < md->n_layers; ++l) {
+    std::memcpy(flat.data() + a.off_w[l], md->W[l], (size_t)a.dims[l] * a.dims[l + 1] * sizeof(float));
+    std::memcpy(flat.data() + a.off_b[l], md->b[l], (size_t)a.dims[l + 1] * sizeof(float));
+  }
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = upload(&t->params, flat.data(), np);
+  if (e == hipSuccess) e = dalloc(&t->m, np);
+  if (e == hipSuccess) e = hipMemset(t->m, 0, np * sizeof(float));
+  if (e == hipSuccess) e = dalloc(&t->v, np);
+  if (e == hipSuccess) e = hipMemset(t->v, 0, np * sizeof(float));
+  if (e == hipSuccess) e = dalloc(&t->partial, (size_t)TRAIN_MAX_GROUPS * np);
+  if (e == hipSuccess) e = dalloc(&t->loss_partial, (size_t)TRAIN_MAX_GROUPS * 2);
+  if (e == hipSuccess) e = dalloc(&t->scalars, (size_t)2);
+  if (e != hipSuccess) {
+    delete t;
+    return fail(MV_ERR_HIP, std::string("mv_train_create: ") + hipGetErrorString(e));
+  }
+  a.params = t->params;
+  a.partial = t->partial;
+  a.loss_partial = t->loss_partial;
+  *out = t;
+  return MV_OK;
+}
+
+void mv_train_destroy(mv_train* t) { delete t; }
+
+static AdamArgs train_reduce_args(const mv_train* t, const TrainArgs& a) {
+  AdamArgs r{};
+  r.n_params = a.n_params;
+  r.groups = a.groups;
+  r.partial = t->partial;
+  r.loss_partial = t->loss_partial;
+  r.rows = (float)a.n;
+  return r;
+}
+
+int mv_train_steps(mv_train* t, int32_t n, const float* x, const int32_t* y, const int32_t* perm,
+                   int32_t first_row, int32_t batch, int32_t n_steps, float* step_losses,
+                   void* stream) {
+  if (!t || n < 1 || !x || !y) return fail(MV_ERR_ARG, "bad mv_train_steps");
+  if (batch < 1) return fail(MV_ERR_ARG, "mv_train_steps: batch < 1");
+  if (n_steps < 0) return fail(MV_ERR_ARG, "mv_train_steps: n_steps < 0");
+  if (first_row < 0 || first_row >= n) return fail(MV_ERR_ARG, "mv_train_steps: first_row outside [0, n)");
+  if (n_steps > 0 && (int64_t)first_row + (int64_t)(n_steps - 1) * batch >= n)
+    return fail(MV_ERR_ARG, "mv_train_steps: a step starts past the last row");
+  if (!on_device(x, t->device) || !on_device(y, t->device) || !on_device(perm, t->device) ||
+      !on_device(step_losses, t->device))
+    return fail(MV_ERR_ARG, "mv_train_steps: a buffer lives on another device than the trainer");
+  HIPCHK(hipSetDevice(t->device));
+  TrainArgs a = t->a;
+  a.n_total = n;
+  a.x = x;
+  a.y = y;
+  a.perm = perm;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  if (t->profiling)
+    for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+  for (int s = 0; s < n_steps; ++s) {
+    a.first = first_row + s * batch;
+    a.n = std::min(batch, n - a.first);
+    if (t->profiling) HIPCHK(hipEventRecord(ev[0], (hipStream_t)stream));
+    HIPCHK(launch_train_grad(a, (hipStream_t)stream));
+    if (t->profiling) HIPCHK(hipEventRecord(ev[1], (hipStream_t)stream));
+    const int64_t k = ++t->step;
+    AdamArgs r = train_reduce_args(t, a);
+    r.params = t->params;
+    r.m = t->m;
+    r.v = t->v;
+    r.beta1 = (float)t->opt.beta1;
+    r.beta2 = (float)t->opt.beta2;
+    r.epsilon = (float)t->opt.epsilon;
+    // Keras: lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), in fp64, rounded to fp32 once
+    r.lr_t = (float)(t->opt.lr * std::sqrt(1.0 - std::pow(t->opt.beta2, (double)k)) /
+                     (1.0 - std::pow(t->opt.beta1, (double)k)));
+    r.loss_out = step_losses ? step_losses + s : nullptr;
+    HIPCHK(launch_train_adam(r, (hipStream_t)stream));
+    if (t->profiling) {  // serialises the steps: for the time split only
+      float g = 0.f, u = 0.f;
+      HIPCHK(hipEventRecord(ev[2], (hipStream_t)stream));
+      HIPCHK(hipEventSynchronize(ev[2]));
+      HIPCHK(hipEventElapsedTime(&g, ev[0], ev[1]));
+      HIPCHK(hipEventElapsedTime(&u, ev[1], ev[2]));
+      t->grad_ms += g;
+      t->adam_ms += u;
+      ++t->timed_steps;
+    }
+  }
+  for (auto& e : ev)
+    if (e) (void)hipEventDestroy(e);
+  return MV_OK;
+}
+
+int mv_train_set_profiling(mv_train* t, int32_t on) {
+  if (!t) return fail(MV_ERR_ARG, "bad mv_train_set_profiling");
+  t->profiling = on != 0;
+  t->grad_ms = t->adam_ms = 0.0;
+  t->timed_steps = 0;
+  return MV_OK;
+}
+
+int mv_train_get_kernel_times(mv_train* t, double* grad_ms, double* adam_ms, int64_t* steps) {
+  if (!t || !grad_ms || !adam_ms || !steps) return fail(MV_ERR_ARG, "bad mv_train_get_kernel_times");
+  *grad_ms = t->grad_ms;
+  *adam_ms = t->adam_ms;
+  *steps = t->timed_steps;
+  return MV_OK;
+}
+
+int mv_train_eval(mv_train* t, int32_t n, const float* x, const int32_t* y, float* out,
+                  void* stream) {
+  if (!t || n < 1 || !x || !y || !out) return fail(MV_ERR_ARG, "bad mv_train_eval");
+  if (!on_device(x, t->device) || !on_device(y, t->device) || !on_device(out, t->device))
+    return fail(MV_ERR_ARG, "mv_train_eval: a buffer lives on another device than the trainer");
+  HIPCHK(hipSetDevice(t->device));
+  TrainArgs a = t->a;
+  a.n_total = a.n = n;
+  a.first = 0;
+  a.x = x;
+  a.y = y;
+  a.perm = nullptr;
+  HIPCHK(launch_train_eval(a, (hipStream_t)stream));
+  AdamArgs r = train_reduce_args(t, a);
+  r.partial = nullptr;
+  r.loss_out = out;
+  r.correct_out = out + 1;
+  HIPCHK(launch_train_adam(r, (hipStream_t)stream));
+  return MV_OK;
+}
+
+int mv_train_grad(mv_train* t, int32_t n, const float* x, const int32_t* y, const int32_t* perm,
+                  float* grad, float* loss, void* stream) {
+  if (!t || n < 1 || !x || !y || !grad) return fail(MV_ERR_ARG, "bad mv_train_grad");
+  if (!on_device(x, t->device) || !on_device(y, t->device) || !on_device(perm, t->device) ||
+      !on_device(grad, t->device) || !on_device(loss, t->device))
+    return fail(MV_ERR_ARG, "mv_train_grad: a buffer lives on another device than the trainer");
+  HIPCHK(hipSetDevice(t->device));
+  TrainArgs a = t->a;
+  a.n_total = a.n = n;
+  a.first = 0;
+  a.x = x;
+  a.y = y;
+  a.perm = perm;
+  HIPCHK(launch_train_grad(a, (hipStream_t)stream));
+  AdamArgs r = train_reduce_args(t, a);
+  r.grad_out = grad;
+  r.loss_out = loss;
+  HIPCHK(launch_train_adam(r, (hipStream_t)stream));
+  return MV_OK;
+}
+
+int mv_train_get(mv_train* t, float* const* W, float* const* b) {
+  if (!t || !W || !b) return fail(MV_ERR_ARG, "bad mv_train_get");
+  HIPCHK(hipSetDevice(t->device));
+  const TrainArgs& a = t->a;
+  std::vector<float> flat((size_t)a.n_params);
+  HIPCHK(hipMemcpy(flat.data(), t->params, flat.size() * sizeof(float), hipMemcpyDeviceToHost));
+  for (int l = 0; l < a.n_layers; ++l) {
+    if (!W[l] || !b[l]) return fail(MV_ERR_ARG, "mv_train_get: null layer array");
+    std::memcpy(W[l], flat.data() + a.off_w[l], (size_t)a.dims[l] * a.dims[l + 1] * sizeof(float));
+    std::memcpy(b[l], flat.data() + a.off_b[l], (size_t)a.dims[l + 1] * sizeof(float));
+  }
+  return MV_OK;
+}
+
+int mv_train_get_state(mv_train* t, float* m, float* v, int64_t* step) {
+  if (!t) return fail(MV_ERR_ARG, "bad mv_train_get_state");
+  HIPCHK(hipSetDevice(t->device));
+  const size_t bytes = (size_t)t->a.n_params * sizeof(float);
+  if (m) HIPCHK(hipMemcpy(m, t->m, bytes, hipMemcpyDeviceToHost));
+  if (v) HIPCHK(hipMemcpy(v, t->v, bytes, hipMemcpyDeviceToHost));
+  if (step) *step = t->step;
+  return MV_OK;
+}
+
+int mv_train_set_state(mv_train* t, const float* m, const float* v, int64_t step) {
+  if (!t || !m || !v || step < 0) return fail(MV_ERR_ARG, "bad mv_train_set_state");
+  HIPCHK(hipSetDevice(t->device));
+  const size_t bytes = (size_t)t->a.n_params * sizeof(float);
+  HIPCHK(hipMemcpy(t->m, m, bytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(t->v, v, bytes, hipMemcpyHostToDevice));
+  t->step = step;
   return MV_OK;
 }
 

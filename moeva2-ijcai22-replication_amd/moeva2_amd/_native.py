@@ -38,6 +38,9 @@ EXPORTED = [
     "mv_objcalc_score", "mv_det_pow", "mv_debug_checks", "mv_set_state_streams",
     "mv_debug_survival_dump", "mv_get_stored_genes", "mv_gene_layout", "mv_set_gene_layout",
     "mv_pgd_create", "mv_pgd_destroy", "mv_pgd_grad", "mv_pgd_run", "mv_pgd_repair",
+    "mv_train_create", "mv_train_destroy", "mv_train_steps", "mv_train_eval", "mv_train_grad",
+    "mv_train_get", "mv_train_get_state", "mv_train_set_state", "mv_train_set_profiling",
+    "mv_train_get_kernel_times",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -92,6 +95,11 @@ class PgdParams(C.Structure):
 
 
 PGD_LOSS_FLIP, PGD_LOSS_CONSTRAINTS = 1, 2
+
+
+class TrainOpt(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("epsilon", C.c_double)]
 
 
 class NativeError(RuntimeError):
@@ -155,6 +163,16 @@ def lib():
             "mv_pgd_grad": [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp],
             "mv_pgd_run": [vp, C.POINTER(PgdParams), C.c_int32, vp, vp, vp, vp],
             "mv_pgd_repair": [vp, C.c_int32, vp, vp],
+            "mv_train_create": [C.c_int32, C.POINTER(ModelDesc), C.POINTER(TrainOpt),
+                                C.POINTER(vp)],
+            "mv_train_steps": [vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp],
+            "mv_train_eval": [vp, C.c_int32, vp, vp, vp, vp],
+            "mv_train_grad": [vp, C.c_int32, vp, vp, vp, vp, vp, vp],
+            "mv_train_get": [vp, C.POINTER(_f32p), C.POINTER(_f32p)],
+            "mv_train_get_state": [vp, _f32p, _f32p, C.POINTER(C.c_int64)],
+            "mv_train_set_state": [vp, _f32p, _f32p, C.c_int64],
+            "mv_train_set_profiling": [vp, C.c_int32],
+            "mv_train_get_kernel_times": [vp, _f64p, _f64p, C.POINTER(C.c_int64)],
         }
         for name, args in sig.items():
             try:
@@ -171,6 +189,8 @@ def lib():
         L.mv_objcalc_destroy.restype = None
         L.mv_pgd_destroy.argtypes = [vp]
         L.mv_pgd_destroy.restype = None
+        L.mv_train_destroy.argtypes = [vp]
+        L.mv_train_destroy.restype = None
         _LIB = L
     return _LIB
 
@@ -678,6 +698,93 @@ class Pgd:
     def repair(self, x, stream=None):
         """fix_features_types on feature-space rows x (n, D) fp32, in place."""
         check(lib().mv_pgd_repair(self._h, int(x.shape[0]), _ptr(x), _stream(stream)))
+
+
+class Trainer:
+    """Device training of a Dense(relu)...Dense(softmax) model (mv_train_*): Adam on the mean
+    cross-entropy, one per (device, model).  Flat arrays hold, per layer, W row-major
+    (in, out) then b."""
+
+    def __init__(self, weights, biases, lr=1e-3, beta1=0.9, beta2=0.999, epsilon=1e-7, device=0):
+        keep = []
+        md = _model_desc(weights, biases, keep)
+        opt = TrainOpt(float(lr), float(beta1), float(beta2), float(epsilon))
+        self._h = C.c_void_p()
+        check(lib().mv_train_create(device, C.byref(md), C.byref(opt), C.byref(self._h)))
+        self.device = device
+        self.dims = [int(weights[0].shape[0])] + [int(w.shape[1]) for w in weights]
+        self.n_params = sum(k * n + n for k, n in zip(self.dims[:-1], self.dims[1:]))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _LIB is not None:
+            _LIB.mv_train_destroy(h)
+            self._h = None
+
+    def steps(self, x, y, batch, n_steps, first_row=0, perm=None, step_losses=None, stream=None):
+        """x (n, D) fp32, y (n,) int32, perm (n,) int32 or None: n_steps Adam steps."""
+        check(lib().mv_train_steps(self._h, int(x.shape[0]), _ptr(x), _ptr(y), _ptr(perm),
+                                   int(first_row), int(batch), int(n_steps), _ptr(step_losses),
+                                   _stream(stream)))
+
+    def eval(self, x, y, out, stream=None):
+        """out (2,) fp32 device tensor <- (mean cross-entropy, argmax-correct rows)."""
+        check(lib().mv_train_eval(self._h, int(x.shape[0]), _ptr(x), _ptr(y), _ptr(out),
+                                  _stream(stream)))
+
+    def grad(self, x, y, grad, loss=None, perm=None, stream=None):
+        """The mean cross-entropy's gradient over all rows: grad (n_params,), loss (1,)."""
+        check(lib().mv_train_grad(self._h, int(x.shape[0]), _ptr(x), _ptr(y), _ptr(perm),
+                                  _ptr(grad), _ptr(loss), _stream(stream)))
+
+    def get(self):
+        """(weights, biases) as host fp32 arrays; synchronises the device."""
+        import torch
+
+        torch.cuda.synchronize(self.device)
+        W = [np.empty((k, n), np.float32) for k, n in zip(self.dims[:-1], self.dims[1:])]
+        b = [np.empty(n, np.float32) for n in self.dims[1:]]
+        n = len(W)
+        check(lib().mv_train_get(self._h, (_f32p * n)(*[w.ctypes.data_as(_f32p) for w in W]),
+                                 (_f32p * n)(*[v.ctypes.data_as(_f32p) for v in b])))
+        return W, b
+
+    def get_state(self):
+        """(m, v, step): Adam's flat moments and the step count; synchronises the device."""
+        import torch
+
+        torch.cuda.synchronize(self.device)
+        m, v = np.empty(self.n_params, np.float32), np.empty(self.n_params, np.float32)
+        step = C.c_int64(0)
+        check(lib().mv_train_get_state(self._h, m.ctypes.data_as(_f32p), v.ctypes.data_as(_f32p),
+                                       C.byref(step)))
+        return m, v, int(step.value)
+
+    def set_state(self, m, v, step):
+        import torch
+
+        torch.cuda.synchronize(self.device)
+        m, v = _arr(m, np.float32), _arr(v, np.float32)
+        if m.shape != (self.n_params,) or v.shape != (self.n_params,):
+            raise ValueError("set_state: m and v are flat (n_params,) arrays")
+        check(lib().mv_train_set_state(self._h, m.ctypes.data_as(_f32p), v.ctypes.data_as(_f32p),
+                                       int(step)))
+
+    def set_profiling(self, on: bool):
+        check(lib().mv_train_set_profiling(self._h, int(bool(on))))
+
+    def kernel_times(self):
+        """Device ms in k_train_grad / k_train_adam over the profiled steps."""
+        g, u, n = C.c_double(), C.c_double(), C.c_int64()
+        check(lib().mv_train_get_kernel_times(self._h, C.byref(g), C.byref(u), C.byref(n)))
+        return {"grad_ms": g.value, "adam_ms": u.value, "steps": int(n.value)}
+
+
+def flatten_params(weights, biases) -> np.ndarray:
+    """The flat parameter layout of mv_train_*: per layer W row-major (in, out), then b."""
+    return np.concatenate([np.concatenate([np.asarray(w, np.float32).ravel(),
+                                           np.asarray(b, np.float32).ravel()])
+                           for w, b in zip(weights, biases)])
 
 
 _MLPS = {}

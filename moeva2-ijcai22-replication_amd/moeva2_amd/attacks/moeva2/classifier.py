@@ -29,6 +29,18 @@ class DenseMLPModel:
 
         return predict_proba(self.mlp, x)
 
+    def save(self, path: str) -> str:
+        """Write the ``.npz`` that ``load_model`` reads (W{i}, b{i}, activations); returns
+        the file's path (``.npz`` is appended to a path without it)."""
+        if not path.endswith(".npz"):
+            path = path + ".npz"
+        arrays = {"activations": np.array(list(self.mlp.activations))}
+        for i, (w, b) in enumerate(zip(self.mlp.weights, self.mlp.biases)):
+            arrays[f"W{i}"] = np.asarray(w, np.float32)
+            arrays[f"b{i}"] = np.asarray(b, np.float32)
+        np.savez(path, **arrays)
+        return path
+
 
 def load_model(path: str) -> DenseMLPModel:
     if os.path.isdir(path):

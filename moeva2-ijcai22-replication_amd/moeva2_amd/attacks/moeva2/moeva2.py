@@ -152,7 +152,10 @@ class Moeva2:
 
     def _get_classifier(self):
         if self._classifier is None:
-            self._classifier = Classifier(load_model(self._classifier_path))
+            # engine extension: a model object (a freshly trained DenseMLPModel) in place of
+            # the path of a saved one
+            path = self._classifier_path
+            self._classifier = Classifier(load_model(path) if isinstance(path, str) else path)
         return self._classifier
 
     def pop_size(self) -> int:
