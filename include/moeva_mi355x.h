@@ -236,6 +236,48 @@ int mv_objcalc_run(mv_objcalc* o, mv_engine* constraints, mv_mlp* classifier, in
 int mv_objcalc_score(mv_objcalc* o, int32_t B, int32_t n, const double* x_init, const double* x,
                      const double* G, int32_t C, const double* proba, int32_t n_out,
                      int32_t minimize_class, double* obj, int32_t* range_bad, void* stream);
+/* ---- Tree-ensemble classifiers (engine extension; the reference takes any predict_proba
+ * model, classifier.py:11-29): scikit-learn's RandomForestClassifier / ExtraTreesClassifier /
+ * DecisionTreeClassifier predict_proba, restated in moeva2_amd/models/forest.py.  A row is
+ * cast to fp32 (as sklearn casts X); at an inner node it goes left when (double)x[feature] <=
+ * threshold, else right (so a NaN goes right); the probability is the fp64 sum of the trees'
+ * leaf rows in tree order, starting from 0.0, divided by n_trees.
+ * Tables (host arrays): the nodes of tree t are tree_root[t] .. tree_root[t+1]-1, root first.
+ * A node with feature < 0 is a leaf whose row is leaf_value[-feature - 1].
+ * Refused with MV_ERR_ARG: n_classes outside 2..8, n_trees < 1, n_nodes above INT32_MAX, a
+ * split feature outside [0, n_features), a leaf index outside leaf_value, a child index that
+ * is not greater than its parent's or lies outside its own tree (so no walk can cycle), a
+ * node with two parents.  The device only walks checked tables. */
+typedef struct mv_forest_desc {
+  int32_t n_features;         /* D: the width of a row */
+  int32_t n_classes;          /* 2..8 */
+  int32_t n_trees;
+  int32_t n_leaves;
+  int64_t n_nodes;
+  const int32_t* feature;     /* host [n_nodes] split feature, or -(leaf index) - 1 */
+  const double* threshold;    /* host [n_nodes] */
+  const int32_t* left;        /* host [n_nodes] (unused at a leaf) */
+  const int32_t* right;       /* host [n_nodes] */
+  const int32_t* tree_root;   /* host [n_trees], ascending from 0 */
+  const double* leaf_value;   /* host [n_leaves][n_classes]: value / normalizer, fp64 */
+} mv_forest_desc;
+typedef struct mv_forest mv_forest;
+/* Classifier.predict_proba for a forest (the mv_mlp_* analogue): x dev [n][n_features]
+ * (ML-scaled, fp64) -> proba dev [n][n_classes] fp64, the restatement's bits. */
+int mv_forest_create(int32_t device, const mv_forest_desc* forest, mv_forest** out);
+void mv_forest_destroy(mv_forest* f);
+int mv_forest_predict(mv_forest* f, int32_t n, const double* x, double* proba, void* stream);
+/* Make a forest the engine's classifier: mv_evaluate, mv_attack_run and the history then take
+ * f1 = proba[minimize_class] from k_forest where they take it from an MLP kernel otherwise
+ * (mv_get_mlp_kernel reports 8).  Only on an engine created with model == NULL, once, and
+ * before mv_set_states (MV_ERR_STATE otherwise; no device call is made then);
+ * forest->n_features must be the problem's D.  The engine keeps the full gene layout. */
+int mv_engine_set_forest(mv_engine* e, const mv_forest_desc* forest);
+/* mv_objcalc_run with a forest as the classifier. */
+int mv_objcalc_run_forest(mv_objcalc* o, mv_engine* constraints, mv_forest* classifier,
+                          int32_t B, int32_t n, const double* x_init, const double* x,
+                          int32_t minimize_class, double* obj, int32_t* range_bad, void* stream);
+
 typedef struct mv_attack_params {
   int32_t n_gen;          /* Moeva2 n_gen (termination "n_gen") */
   int32_t pop_size;       /* P = n_ref_points + n_obj (203 for n_pop 200) */
@@ -350,7 +392,8 @@ int mv_get_row_kernel(mv_engine* e, int32_t* kind);
 /* The classifier kernel an attack generation runs: 0 = k_mlp (one tile of rows per
  * workgroup, any widths), 1 = k_mlp2 reading the child genes (no fp32 ML row is written),
  * 2 = k_mlp2 reading the fp32 ML rows, 4 = k_mlpw (bf16 weights), 5 = k_mlpw32 (fp32 wide
- * nets: 64-row tiles, one activation buffer), -1 = no device classifier
+ * nets: 64-row tiles, one activation buffer), 6 / 7 = k_mlpr reading the genes / the fp32 ML
+ * rows, 8 = k_forest (a tree ensemble, mv_engine_set_forest), -1 = no device classifier
  * (3, the retired k_mlp2x, is no longer returned).
  * Lets a profiler price the ML-row bytes of the row kernel and the classifier. */
 int mv_get_mlp_kernel(mv_engine* e, int32_t* kind);

@@ -174,6 +174,7 @@ struct mv_engine {
   int* off_scr = nullptr;
   bool attack_ready = false;
   bool has_model = false;
+  bool has_forest = false;  // mv_engine_set_forest: k_forest is the classifier (p.forest)
   long long* d_phase = nullptr;  // MV_SURV_PHASES=1: survival phase clocks [B][16]
   long long* d_gphase = nullptr; // MV_GEN_PHASES=1: k_genc clocks [grid][8] (one group)
   bool gphase_mlp = false;        // MV_MLP_PHASES=1: the same buffer holds the classifier's
@@ -822,7 +823,9 @@ int mv_set_states(mv_engine* e, int32_t B, const double* x_init, const double* x
     return fail(MV_ERR_ARG, "bad mv_set_states arguments");
   HIPCHK(hipSetDevice(e->device));
   // a model-less engine (host classifier plugin) evaluates f2 / f3 only: no class check
-  const int nout = e->has_model ? e->p.dims[e->p.n_layers] : INT32_MAX;
+  const int nout = e->has_model    ? e->p.dims[e->p.n_layers]
+                   : e->has_forest ? e->p.forest.n_classes
+                                   : INT32_MAX;
   for (int b = 0; b < B; ++b)
     if (minimize_class[b] < 0 || minimize_class[b] >= nout)
       return fail(MV_ERR_ARG, "minimize_class out of range");
@@ -867,6 +870,16 @@ int mv_set_states(mv_engine* e, int32_t B, const double* x_init, const double* x
   if (err == hipSuccess) err = e->keep(e->state_allocs, &dxu, xu, (size_t)B * e->p.D);
   if (err == hipSuccess)
     err = e->keep(e->state_allocs, (int**)&e->s.min_class, minimize_class, (size_t)B);
+  if (err == hipSuccess && e->has_forest) {
+    // the fp32 ML row of every state for the features the attack does not move: the row
+    // kernels' expression for xml, so a split sees the same rounding on either side
+    const int D = e->p.D;
+    std::vector<float> xfix((size_t)B * D);
+    for (int b = 0; b < B; ++b)
+      for (int f = 0; f < D; ++f)
+        xfix[(size_t)b * D + f] = (float)(x_init[(size_t)b * D + f] * e->hp.mls[f] + e->hp.mlm[f]);
+    err = e->keep(e->state_allocs, (float**)&e->s.xfix, xfix.data(), xfix.size());
+  }
   if (err != hipSuccess) return fail(MV_ERR_HIP, std::string("alloc: ") + hipGetErrorString(err));
   int slot = 0;
   HIPCHK(stage_rows(base_rows(e), (hipStream_t)stream, &slot));
@@ -1072,7 +1085,7 @@ static int ensure_events(std::vector<hipEvent_t>& v, size_t n) {
 
 int mv_attack_run(mv_engine* e, const mv_attack_params* prm, void* stream_) {
   if (!e || !prm) return fail(MV_ERR_ARG, "null argument");
-  if (!e->has_model)
+  if (!e->has_model && !e->has_forest)
     return fail(MV_ERR_STATE, "mv_attack_run needs a device classifier (hosted plugins run "
                               "the generation loop from the host)");
   if (e->B <= 0) return fail(MV_ERR_STATE, "no states bound (mv_set_states)");
@@ -1221,6 +1234,7 @@ int mv_attack_run(mv_engine* e, const mv_attack_params* prm, void* stream_) {
     r.s.sblob += b0 * sbb;
     r.s.bias1 += b0 * H1;
     r.s.min_class += b0;
+    if (r.s.xfix) r.s.xfix += b0 * D;
     r.total = r.s.B * n_per_state;
     r.key0 += (uint32_t)b0;  // per-state streams: the group's first state
     if (r.genes_in) r.genes_in += b0 * r.in_rows * V;
@@ -1795,19 +1809,23 @@ static hipError_t grow(double** p, size_t* cap, size_t n) {
   return e;
 }
 
-int mv_objcalc_run(mv_objcalc* o, mv_engine* e, mv_mlp* m, int32_t B, int32_t n,
-                   const double* x_init, const double* x, int32_t minimize_class, double* obj,
-                   int32_t* range_bad, void* stream_) {
-  if (!o || !e || !m || B < 0 || n < 0) return fail(MV_ERR_ARG, "bad mv_objcalc_run arguments");
-  if (e->p.D != o->D || m->a.dims[0] != o->D)
+}  // extern "C"
+
+// mv_objcalc_run / mv_objcalc_run_forest: the classifier is `predict(rows, x_ml, proba)`, of
+// input width clf_D and n_out classes, on device clf_device.
+template <class Predict>
+static int objcalc_run(mv_objcalc* o, mv_engine* e, int clf_D, int n_out, int clf_device,
+                       Predict&& predict, int32_t B, int32_t n, const double* x_init,
+                       const double* x, int32_t minimize_class, double* obj, int32_t* range_bad,
+                       void* stream_) {
+  if (e->p.D != o->D || clf_D != o->D)
     return fail(MV_ERR_ARG, "constraints / classifier / scaler feature counts differ");
-  const int n_out = m->a.dims[m->a.n_layers];
   if (minimize_class < 0 || minimize_class >= (n_out == 1 ? 2 : n_out))
     return fail(MV_ERR_ARG, "minimize_class outside the classifier output");
   const long total = (long)B * n;
   if (total == 0) return MV_OK;
   if (!x_init || !x || !obj || !range_bad) return fail(MV_ERR_ARG, "null buffer");
-  if (e->device != o->device || m->device != o->device)
+  if (e->device != o->device || clf_device != o->device)
     return fail(MV_ERR_ARG, "objects live on different devices");
   if (!on_device(x_init, o->device) || !on_device(x, o->device) || !on_device(obj, o->device) ||
       !on_device(range_bad, o->device))
@@ -1828,11 +1846,7 @@ int mv_objcalc_run(mv_objcalc* o, mv_engine* e, mv_mlp* m, int32_t B, int32_t n,
     HIPCHK(launch_constraints(e->p, slot, (int)total, x, o->G, stream));
     HIPCHK(release_rows(slot, stream));
   }
-  MlpArgs ma = m->a;
-  ma.n = (int)total;
-  ma.x = xml;
-  ma.proba = o->proba;
-  HIPCHK(launch_predict(ma, stream));
+  HIPCHK(predict((int)total, xml, o->proba, stream));
   ObjArgs a{};
   a.total = total;
   a.n = n;
@@ -1853,6 +1867,220 @@ int mv_objcalc_run(mv_objcalc* o, mv_engine* e, mv_mlp* m, int32_t B, int32_t n,
   a.obj = obj;
   a.range_bad = range_bad;
   HIPCHK(launch_objectives(a, stream));
+  return MV_OK;
+}
+
+// ---- tree ensembles (forest.hip)
+
+// The limits of a forest's tables, checked before anything is uploaded: 2..8 classes, at
+// least one tree, split features in [0, D), leaf indices inside leaf_value, every child inside
+// its own tree and after its parent (no walk can cycle), node count within int32.
+static int forest_check(const mv_forest_desc* d) {
+  if (!d || !d->feature || !d->threshold || !d->left || !d->right || !d->tree_root ||
+      !d->leaf_value)
+    return fail(MV_ERR_ARG, "forest: null table");
+  if (d->n_classes < 2 || d->n_classes > FOREST_MAX_CLASSES)
+    return fail(MV_ERR_ARG, "forest: 2..8 classes");
+  if (d->n_trees < 1) return fail(MV_ERR_ARG, "forest: at least one tree");
+  if (d->n_features < 1) return fail(MV_ERR_ARG, "forest: n_features must be positive");
+  if (d->n_nodes < d->n_trees || d->n_nodes > (int64_t)INT32_MAX)
+    return fail(MV_ERR_ARG, "forest: the node count must fit int32 (and hold every root)");
+  if (d->n_leaves < 1) return fail(MV_ERR_ARG, "forest: no leaf");
+  const int64_t N = d->n_nodes;
+  if (d->tree_root[0] != 0) return fail(MV_ERR_ARG, "forest: tree_root must start at 0");
+  for (int t = 0; t < d->n_trees; ++t) {
+    const int64_t lo = d->tree_root[t], hi = t + 1 < d->n_trees ? d->tree_root[t + 1] : N;
+    if (lo < 0 || lo >= hi || hi > N)
+      return fail(MV_ERR_ARG, "forest: tree_root must ascend inside the node array");
+    for (int64_t i = lo; i < hi; ++i) {
+      const int f = d->feature[i];
+      if (f < 0) {
+        if (-(int64_t)f - 1 >= d->n_leaves)
+          return fail(MV_ERR_ARG, "forest: a leaf index lies outside leaf_value");
+        continue;
+      }
+      if (f >= d->n_features)
+        return fail(MV_ERR_ARG, "forest: a split feature lies outside [0, n_features)");
+      for (const int64_t c : {(int64_t)d->left[i], (int64_t)d->right[i]}) {
+        if (c <= i) return fail(MV_ERR_ARG, "forest: a child index is not greater than its parent's");
+        if (c >= hi) return fail(MV_ERR_ARG, "forest: a child index lies outside its tree");
+      }
+    }
+  }
+  return MV_OK;
+}
+
+// Device form of checked tables: each tree's reachable nodes renumbered breadth first, the two
+// children of a node next to each other (right = left + 1).  slot_of(feature) names where an
+// inner node's value lives (forest.h ForestNode).
+template <class SlotOf>
+static int forest_pack(const mv_forest_desc* d, SlotOf&& slot_of, std::vector<ForestNode>& nodes,
+                       std::vector<int>& roots) {
+  nodes.clear();
+  roots.clear();
+  std::vector<int> order;  // new position in the tree -> old node
+  std::vector<char> seen;  // old node (relative to its tree's root) has a parent
+  for (int t = 0; t < d->n_trees; ++t) {
+    const int lo = d->tree_root[t];
+    const size_t size = (size_t)((t + 1 < d->n_trees ? d->tree_root[t + 1] : (int)d->n_nodes) - lo);
+    const size_t base = nodes.size();
+    roots.push_back((int)base);
+    order.assign(1, lo);
+    seen.assign(size, 0);
+    for (size_t i = 0; i < order.size(); ++i) {
+      const int old = order[i];
+      ForestNode nd{};
+      if (d->feature[old] < 0) {
+        nd.slot = d->feature[old];  // ~leaf
+      } else {
+        // a node reached along two paths: not a tree (and copies of a shared subtree could
+        // outgrow the tables)
+        for (const int c : {d->left[old], d->right[old]}) {
+          if (seen[(size_t)(c - lo)]) return fail(MV_ERR_ARG, "forest: a node has two parents");
+          seen[(size_t)(c - lo)] = 1;
+        }
+        nd.threshold = d->threshold[old];
+        nd.slot = slot_of(d->feature[old]);
+        nd.left = (int)(base + order.size());
+        order.push_back(d->left[old]);
+        order.push_back(d->right[old]);
+      }
+      nodes.push_back(nd);
+    }
+  }
+  return MV_OK;
+}
+
+struct mv_forest {
+  int device = 0;
+  int D = 0;
+  DForest f{};
+  std::vector<void*> allocs;
+  ~mv_forest() {
+    (void)hipSetDevice(device);
+    for (void* x : allocs) (void)hipFree(x);
+  }
+};
+
+static hipError_t forest_upload(const mv_forest_desc* d, const std::vector<ForestNode>& nodes,
+                                const std::vector<int>& roots, DForest& f,
+                                std::vector<void*>& allocs) {
+  hipError_t err = hipSuccess;
+  auto K = [&](auto** dst, const auto* host, size_t n) {
+    if (err != hipSuccess) return;
+    err = upload(dst, host, n);
+    if (err == hipSuccess) allocs.push_back((void*)*dst);
+  };
+  f = DForest{};
+  K((ForestNode**)&f.nodes, nodes.data(), nodes.size());
+  K((int**)&f.tree_root, roots.data(), roots.size());
+  K((double**)&f.leaf_value, d->leaf_value, (size_t)d->n_leaves * d->n_classes);
+  f.n_nodes = (int)nodes.size();
+  f.n_trees = d->n_trees;
+  f.n_leaves = d->n_leaves;
+  f.n_classes = d->n_classes;
+  return err;
+}
+
+extern "C" {
+
+int mv_objcalc_run(mv_objcalc* o, mv_engine* e, mv_mlp* m, int32_t B, int32_t n,
+                   const double* x_init, const double* x, int32_t minimize_class, double* obj,
+                   int32_t* range_bad, void* stream_) {
+  if (!o || !e || !m || B < 0 || n < 0) return fail(MV_ERR_ARG, "bad mv_objcalc_run arguments");
+  auto predict = [&](int rows, const double* xm, double* proba, hipStream_t st) {
+    MlpArgs ma = m->a;
+    ma.n = rows;
+    ma.x = xm;
+    ma.proba = proba;
+    return launch_predict(ma, st);
+  };
+  return objcalc_run(o, e, m->a.dims[0], m->a.dims[m->a.n_layers], m->device, predict, B, n,
+                     x_init, x, minimize_class, obj, range_bad, stream_);
+}
+
+int mv_objcalc_run_forest(mv_objcalc* o, mv_engine* e, mv_forest* f, int32_t B, int32_t n,
+                          const double* x_init, const double* x, int32_t minimize_class,
+                          double* obj, int32_t* range_bad, void* stream_) {
+  if (!o || !e || !f || B < 0 || n < 0)
+    return fail(MV_ERR_ARG, "bad mv_objcalc_run_forest arguments");
+  auto predict = [&](int rows, const double* xm, double* proba, hipStream_t st) {
+    ForestArgs fa{};
+    fa.f = f->f;
+    fa.total = rows;
+    fa.D = f->D;
+    fa.x = xm;
+    fa.proba = proba;
+    return launch_forest_predict(fa, st);
+  };
+  return objcalc_run(o, e, f->D, f->f.n_classes, f->device, predict, B, n, x_init, x,
+                     minimize_class, obj, range_bad, stream_);
+}
+
+int mv_forest_create(int32_t device, const mv_forest_desc* d, mv_forest** out) {
+  if (!out) return fail(MV_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (const int rc = forest_check(d)) return rc;
+  std::vector<ForestNode> nodes;
+  std::vector<int> roots;
+  if (const int rc = forest_pack(d, [](int feat) { return feat; }, nodes, roots)) return rc;
+  HIPCHK(hipSetDevice(device));
+  mv_forest* f = new mv_forest();
+  f->device = device;
+  f->D = d->n_features;
+  const hipError_t err = forest_upload(d, nodes, roots, f->f, f->allocs);
+  if (err != hipSuccess) {
+    delete f;
+    return fail(MV_ERR_HIP, std::string("upload: ") + hipGetErrorString(err));
+  }
+  *out = f;
+  return MV_OK;
+}
+
+void mv_forest_destroy(mv_forest* f) { delete f; }
+
+int mv_forest_predict(mv_forest* f, int32_t n, const double* x, double* proba, void* stream) {
+  if (!f || n < 0 || (n > 0 && (!x || !proba))) return fail(MV_ERR_ARG, "bad mv_forest_predict");
+  if (!on_device(x, f->device) || !on_device(proba, f->device))
+    return fail(MV_ERR_ARG, "mv_forest_predict: a buffer lives on another device than the forest");
+  HIPCHK(hipSetDevice(f->device));
+  ForestArgs fa{};
+  fa.f = f->f;
+  fa.total = n;
+  fa.D = f->D;
+  fa.x = x;
+  fa.proba = proba;
+  HIPCHK(launch_forest_predict(fa, (hipStream_t)stream));
+  return MV_OK;
+}
+
+int mv_engine_set_forest(mv_engine* e, const mv_forest_desc* d) {
+  if (!e || !d) return fail(MV_ERR_ARG, "null argument");
+  // every refusal comes before the first device call
+  if (e->has_model)
+    return fail(MV_ERR_STATE, "mv_engine_set_forest: the engine was created with an MLP");
+  if (e->has_forest) return fail(MV_ERR_STATE, "mv_engine_set_forest: a forest is already set");
+  if (e->B > 0)
+    return fail(MV_ERR_STATE, "mv_engine_set_forest must come before mv_set_states");
+  if (const int rc = forest_check(d)) return rc;
+  if (d->n_features != e->p.D) return fail(MV_ERR_ARG, "forest: n_features != D");
+  // where a split's value lives: the row's fp32 ML row for a mutable feature (its position
+  // among the mutable features), the state's xfix for every other feature.  The engine keeps
+  // the full gene layout with a forest (compact_allowed needs an MLP), so the mutable features
+  // are the problem's for every bound state set
+  std::vector<int> slot(e->p.D);
+  for (int f = 0; f < e->p.D; ++f) slot[f] = e->p.Dm4 + f;
+  for (int j = 0; j < e->hp.Dm; ++j) slot[e->hp.mut[j]] = j;
+  std::vector<ForestNode> nodes;
+  std::vector<int> roots;
+  if (const int rc = forest_pack(d, [&](int feat) { return slot[feat]; }, nodes, roots)) return rc;
+  HIPCHK(hipSetDevice(e->device));
+  const hipError_t err = forest_upload(d, nodes, roots, e->p.forest, e->prob_allocs);
+  if (err != hipSuccess) {
+    e->p.forest = DForest{};
+    return fail(MV_ERR_HIP, std::string("upload: ") + hipGetErrorString(err));
+  }
+  e->has_forest = true;
   return MV_OK;
 }
 
@@ -1898,13 +2126,14 @@ int mv_debug_checks(int32_t* record, int32_t* compiled) {
   if (!record) return fail(MV_ERR_ARG, "null record");
   if (compiled) *compiled = MV_CHECKS_ON;
   HIPCHK(hipDeviceSynchronize());
-  int ev[8], sv[8], pg[8];
+  int ev[8], sv[8], pg[8], fo[8];
   HIPCHK(take_checks_eval(ev));
   HIPCHK(take_checks_survive(sv));
   HIPCHK(take_checks_pgd(pg));
-  const int* r = ev[0] ? ev : (sv[0] ? sv : pg);
+  HIPCHK(take_checks_forest(fo));
+  const int* r = ev[0] ? ev : (sv[0] ? sv : (pg[0] ? pg : fo));
   for (int k = 0; k < 8; ++k) record[k] = r[k];
-  record[5] = ev[5] + sv[5] + pg[5];
+  record[5] = ev[5] + sv[5] + pg[5] + fo[5];
   return MV_OK;
 }
 

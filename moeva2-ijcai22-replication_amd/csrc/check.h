@@ -48,6 +48,9 @@ enum : int {
                         // the first such state's inputs go to the survival dump
   CK_PGD_TAPE = 27,     // k_pgd / k_pgd_grad: EXPR tape slot (an instruction's ordinal or an
                         // operand link) outside [0, tape)
+  CK_FOREST_NODE = 28,  // k_forest: node index outside [0, n_nodes)
+  CK_FOREST_LEAF = 29,  // k_forest: leaf index outside [0, n_leaves)
+  CK_FOREST_SLOT = 30,  // k_forest: value slot outside the ML row / the state's fixed vector
 };
 // survival dump (checks builds): [0] 1 = valid, [1] gen, [2] state in its group, [3] N,
 // [4, 7) carried ideal, [7, 10) carried worst, [10, 19) carried extremes, [19] has_extreme,
@@ -109,6 +112,7 @@ __device__ __forceinline__ T* chk_ptr(T* p, const T* lo, const T* hi, int code) 
 hipError_t take_checks_eval(int* out);
 hipError_t take_checks_survive(int* out);
 hipError_t take_checks_pgd(int* out);
+hipError_t take_checks_forest(int* out);
 hipError_t take_survival_dump(double* out);  // [SURV_DUMP_N], cleared
 
 }  // namespace mv

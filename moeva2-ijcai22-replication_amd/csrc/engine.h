@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "forest.h"
+
 // MV_CLOCKS (development builds: `make variant NAME=clk DEFS=-DMV_CLOCKS=1`): the k_genc /
 // k_mlp2 / k_survive phase clocks behind MV_GEN_PHASES / MV_MLP_PHASES / MV_SURV_PHASES.
 // Compiled out of the product build, so its kernels carry no clock branches.
@@ -136,6 +138,10 @@ struct DProblem {
   // lane's operands of those ops are LDS addresses held in registers (rowops.h
   // constraints_slim)
   int sd_reg;
+  // a tree ensemble in place of the Dense MLP (mv_engine_set_forest; forest.h): n_layers == 0
+  // and forest.n_trees > 0.  The row kernels write the fp32 ML rows as they do without a
+  // model (xml_direct stays 0) and k_forest reads them
+  DForest forest;
 };
 
 struct DStates {
@@ -147,6 +153,9 @@ struct DStates {
                                // mutable features [Dm4] each, then x_init [D] (kernels.h)
   const float* bias1;       // [B][H1]
   const int* min_class;     // [B]
+  // forest engines: the whole ML row in fp32, (float)(x_init * ml_scale + ml_min), for the
+  // features the attack does not move (the row kernels' expression for xml)
+  const float* xfix;        // [B][D] or NULL
 };
 
 // Row-tile evaluation (optionally preceded by variation) -----------------------------

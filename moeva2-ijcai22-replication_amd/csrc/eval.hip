@@ -2684,6 +2684,25 @@ hipError_t launch_mlp(const RowsArgs& a, int slot, int hist_row0, hipStream_t st
   switch (r.kind) {
     case MLP_NONE:
       return hipSuccess;  // model-less: f1 from the host
+    case FOREST_ROWS: {  // forest.hip k_forest over the fp32 ML rows the row kernel wrote
+      ForestArgs fa{};
+      fa.f = p.forest;
+      fa.total = a.total;
+      fa.D = p.D;
+      fa.n = a.n;
+      fa.Dm4 = p.Dm4;
+      fa.xml = a.xml;
+      fa.xfix = a.s.xfix;
+      fa.min_class = a.s.min_class;
+      fa.out_map = a.out_map;
+      fa.F = a.F;
+      fa.out_rows = a.out_rows;
+      fa.hist = a.hist;
+      fa.hist_rows = a.hist_rows;
+      fa.hist_w = a.hist_w;
+      fa.hist_row0 = hist_row0;
+      return launch_forest_rows(fa, stream);
+    }
     case MLPR_GENES:
     case MLPR_ROWS: {
       const size_t lds = mlpr_lds(p, r.rw).total;

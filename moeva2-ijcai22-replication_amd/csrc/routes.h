@@ -280,6 +280,7 @@ enum MlpKind {
   MLPW32 = 5,       // k_mlpw32 (fp32, wide)
   MLPR_GENES = 6,   // k_mlpr reading the genes (hidden widths <= 64)
   MLPR_ROWS = 7,    // k_mlpr reading the fp32 ML rows (XML instance)
+  FOREST_ROWS = 8,  // k_forest (a tree ensemble) reading the fp32 ML rows and xfix
 };
 struct MlpRoute {
   int kind;     // MlpKind
@@ -294,6 +295,10 @@ struct MlpRoute {
 
 inline MlpRoute mlp_route(const DProblem& p, const Switches& sw) {
   MlpRoute r{};
+  if (p.forest.n_trees > 0) {  // the problem carries trees (mv_engine_set_forest: no MLP then)
+    r.kind = FOREST_ROWS;
+    return r;
+  }
   if (p.n_layers == 0) {
     r.kind = MLP_NONE;
     return r;

@@ -41,6 +41,8 @@ EXPORTED = [
     "mv_train_create", "mv_train_destroy", "mv_train_steps", "mv_train_eval", "mv_train_grad",
     "mv_train_get", "mv_train_get_state", "mv_train_set_state", "mv_train_set_profiling",
     "mv_train_get_kernel_times",
+    "mv_forest_create", "mv_forest_destroy", "mv_forest_predict", "mv_engine_set_forest",
+    "mv_objcalc_run_forest",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -76,6 +78,13 @@ class ObjCalcDesc(C.Structure):
     _fields_ = [("D", C.c_int32), ("n_ohe", C.c_int32), ("ohe_offsets", _i32p),
                 ("ohe_feats", _i32p), ("mm_scale", _f64p), ("mm_min", _f64p),
                 ("ml_scale", _f64p), ("ml_min", _f64p), ("norm", C.c_int32)]
+
+
+class ForestDesc(C.Structure):
+    _fields_ = [("n_features", C.c_int32), ("n_classes", C.c_int32), ("n_trees", C.c_int32),
+                ("n_leaves", C.c_int32), ("n_nodes", C.c_int64), ("feature", _i32p),
+                ("threshold", _f64p), ("left", _i32p), ("right", _i32p), ("tree_root", _i32p),
+                ("leaf_value", _f64p)]
 
 
 class PgdDesc(C.Structure):
@@ -173,6 +182,11 @@ def lib():
             "mv_train_set_state": [vp, _f32p, _f32p, C.c_int64],
             "mv_train_set_profiling": [vp, C.c_int32],
             "mv_train_get_kernel_times": [vp, _f64p, _f64p, C.POINTER(C.c_int64)],
+            "mv_forest_create": [C.c_int32, C.POINTER(ForestDesc), C.POINTER(vp)],
+            "mv_forest_predict": [vp, C.c_int32, vp, vp, vp],
+            "mv_engine_set_forest": [vp, C.POINTER(ForestDesc)],
+            "mv_objcalc_run_forest": [vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp,
+                                      vp, vp],
         }
         for name, args in sig.items():
             try:
@@ -191,8 +205,14 @@ def lib():
         L.mv_pgd_destroy.restype = None
         L.mv_train_destroy.argtypes = [vp]
         L.mv_train_destroy.restype = None
+        if hasattr(L, "mv_forest_destroy"):
+            L.mv_forest_destroy.argtypes = [vp]
+            L.mv_forest_destroy.restype = None
         _LIB = L
     return _LIB
+
+
+MV_ERR_ARG = 1
 
 
 def check(rc: int):
@@ -352,6 +372,16 @@ class Engine:
         self.B = 0
         self.dims = dims if weights is not None else []
         self.n_out = dims[-1] if weights is not None else 0
+        self.forest = None
+
+    def set_forest(self, tables):
+        """Make a tree ensemble (models.forest.ForestTables) the engine's classifier
+        (mv_engine_set_forest): only on an engine built without weights, before set_states.
+        Tables outside the engine's limits raise ValueError."""
+        d, keep = _forest_desc(tables)
+        _check_forest(lib().mv_engine_set_forest(self._h, C.byref(d)))
+        self.forest = tables
+        self.n_out = tables.n_classes
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -480,6 +510,9 @@ class Engine:
         mode: bf16 weights/activations on bf16 MFMA, fp32 accumulation)."""
         if dtype not in ("fp32", "bf16"):
             raise ValueError(f"mlp dtype {dtype!r}: 'fp32' or 'bf16'")
+        if dtype == "bf16" and self.forest is not None:
+            raise ValueError("mlp_dtype='bf16' is the Dense MLP's perf mode; a forest runs in "
+                             "fp64 only")
         check(lib().mv_set_mlp_precision(self._h, 1 if dtype == "bf16" else 0))
         self.mlp_dtype = dtype
 
@@ -508,7 +541,14 @@ class Engine:
                 "gen_ms": ph[0], "cons_ms": ph[1], "generations": n.value,
                 "row_kernel": ("k_gen+k_cons", "k_narrow", "k_genc")[rk.value],
                 "mlp_kernel": {-1: None, 0: "k_mlp", 1: "k_mlp2(genes)", 2: "k_mlp2",
-                               4: "k_mlpw", 5: "k_mlpw32", 6: "k_mlpr(genes)", 7: "k_mlpr"}[mk.value]}
+                               4: "k_mlpw", 5: "k_mlpw32", 6: "k_mlpr(genes)", 7: "k_mlpr",
+                               8: "k_forest"}[mk.value]}
+
+    def mlp_kernel(self) -> int:
+        """mv_get_mlp_kernel's kind (csrc/routes.h MlpKind; 8 = k_forest)."""
+        mk = C.c_int32()
+        check(lib().mv_get_mlp_kernel(self._h, C.byref(mk)))
+        return int(mk.value)
 
 
 def survive(F, ref_points, n_survive, mu, seed, gen, ideal, worst, extreme, has_extreme,
@@ -569,6 +609,54 @@ class Mlp:
         check(lib().mv_mlp_predict(self._h, x.shape[0], _ptr(x), _ptr(proba), _stream(stream)))
 
 
+def _forest_desc(t):
+    """ForestDesc of a models.forest.ForestTables (and the arrays it points into)."""
+    keep = [np.ascontiguousarray(t.feature, np.int32), np.ascontiguousarray(t.threshold, np.float64),
+            np.ascontiguousarray(t.left, np.int32), np.ascontiguousarray(t.right, np.int32),
+            np.ascontiguousarray(t.tree_root, np.int32),
+            np.ascontiguousarray(t.leaf_value, np.float64)]
+    d = ForestDesc()
+    d.n_features = int(t.n_features)
+    d.n_classes = int(keep[5].shape[1]) if keep[5].ndim == 2 else 0
+    d.n_trees = int(keep[4].shape[0])
+    d.n_leaves = int(keep[5].shape[0])
+    d.n_nodes = int(keep[0].shape[0])
+    d.feature = keep[0].ctypes.data_as(_i32p)
+    d.threshold = keep[1].ctypes.data_as(_f64p)
+    d.left = keep[2].ctypes.data_as(_i32p)
+    d.right = keep[3].ctypes.data_as(_i32p)
+    d.tree_root = keep[4].ctypes.data_as(_i32p)
+    d.leaf_value = keep[5].ctypes.data_as(_f64p)
+    return d, keep
+
+
+def _check_forest(rc: int):
+    """MV_ERR_ARG from a forest call is a table outside the limits: ValueError."""
+    if rc == MV_ERR_ARG:
+        raise ValueError(lib().mv_last_error().decode())
+    check(rc)
+
+
+class Forest:
+    """Device tree ensemble for Classifier.predict_proba (mv_forest_*)."""
+
+    def __init__(self, tables, device=0):
+        d, keep = _forest_desc(tables)
+        self._h = C.c_void_p()
+        _check_forest(lib().mv_forest_create(device, C.byref(d), C.byref(self._h)))
+        self.n_out = int(tables.n_classes)
+        self.device = device
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _LIB is not None:
+            _LIB.mv_forest_destroy(h)
+            self._h = None
+
+    def predict(self, x, proba, stream=None):
+        check(lib().mv_forest_predict(self._h, x.shape[0], _ptr(x), _ptr(proba), _stream(stream)))
+
+
 class ObjCalc:
     """Device ObjectiveCalculator._calculate_objective (mv_objcalc_*): one per (type mask,
     min_max_scaler, ml_scaler, norm)."""
@@ -612,9 +700,9 @@ class ObjCalc:
             stream=None):
         """x_init (B, D), x (B, n, D) device tensors -> obj (B, n, 3), range_bad (B, n)."""
         B, n = int(x.shape[0]), int(x.shape[1])
-        check(lib().mv_objcalc_run(self._h, engine._h, mlp._h, B, n, _ptr(x_init), _ptr(x),
-                                   int(minimize_class), _ptr(obj), _ptr(range_bad),
-                                   _stream(stream)))
+        run = lib().mv_objcalc_run_forest if isinstance(mlp, Forest) else lib().mv_objcalc_run
+        check(run(self._h, engine._h, mlp._h, B, n, _ptr(x_init), _ptr(x), int(minimize_class),
+                  _ptr(obj), _ptr(range_bad), _stream(stream)))
 
     def score(self, x_init, x, G, proba, minimize_class, obj, range_bad, stream=None):
         """Scoring with a caller-supplied constraint matrix G (B*n, C) (None: C = 0) and
@@ -797,6 +885,24 @@ def predict_proba(mlp, x):
     m = _MLPS.get(id(mlp))
     if m is None:
         m = _MLPS[id(mlp)] = (Mlp(mlp.weights, mlp.biases), mlp)
+    m = m[0]
+    xd = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(x), np.float64)).cuda(m.device)
+    out = torch.empty((xd.shape[0], m.n_out), dtype=torch.float64, device=xd.device)
+    m.predict(xd, out)
+    return out.cpu().numpy()
+
+
+_FORESTS = {}
+
+
+def forest_predict_proba(tables, x):
+    """Host convenience: numpy rows (already ML-scaled) -> a forest's probabilities, on the
+    GPU."""
+    import torch
+
+    m = _FORESTS.get(id(tables))
+    if m is None:
+        m = _FORESTS[id(tables)] = (Forest(tables), tables)
     m = m[0]
     xd = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(x), np.float64)).cuda(m.device)
     out = torch.empty((xd.shape[0], m.n_out), dtype=torch.float64, device=xd.device)

@@ -5,12 +5,17 @@ engine runs on MFMA.
 for the Keras Sequential(Dense...) classifiers shipped with the reference: a SavedModel
 directory is read with the tensor-bundle reader (no TensorFlow), an ``.npz`` produced by
 tools/import_reference_data.py is read directly.
+
+Engine extension: tree ensembles.  A ``.joblib`` file holding a fitted scikit-learn
+RandomForestClassifier / ExtraTreesClassifier / DecisionTreeClassifier, or the ``.npz`` of a
+``models.forest.ForestTables``, loads as a ``ForestModel`` whose trees run on the device.
 """
 import os
 
 import numpy as np
 
 from ...io.tf_bundle import DenseMLP, load_dense_mlp
+from ...models.forest import ForestModel, ForestTables, is_sklearn_trees
 
 
 class DenseMLPModel:
@@ -42,11 +47,22 @@ class DenseMLPModel:
         return path
 
 
-def load_model(path: str) -> DenseMLPModel:
+def load_model(path: str):
     if os.path.isdir(path):
         return DenseMLPModel(load_dense_mlp(path))
+    if path.endswith(".joblib"):
+        # a joblib file is a pickle: load only files you wrote or trust
+        import joblib
+
+        model = joblib.load(path)
+        if not is_sklearn_trees(model):
+            raise ValueError(f"{path} holds a {type(model).__name__}; expected a fitted "
+                             "scikit-learn forest or tree classifier")
+        return ForestModel(ForestTables.from_sklearn(model))
     if path.endswith(".npz") or os.path.exists(path + ".npz"):
         d = np.load(path if path.endswith(".npz") else path + ".npz", allow_pickle=False)
+        if "forest_tables" in d.files:
+            return ForestModel(ForestTables.load(path if path.endswith(".npz") else path + ".npz"))
         n = sum(1 for k in d.files if k.startswith("W"))
         return DenseMLPModel(DenseMLP([d[f"W{i}"] for i in range(n)],
                                       [d[f"b{i}"] for i in range(n)],
@@ -79,3 +95,16 @@ class Classifier:
                 "the MI355X engine runs Dense-MLP classifiers (load_model); got "
                 f"{type(self._classifier).__name__}")
         return self._classifier.dense_weights()
+
+    def forest_tables(self) -> ForestTables:
+        """Tables for the device tree walk (engine extension): the model is a fitted
+        scikit-learn forest / tree classifier, a ForestTables or a ForestModel."""
+        clf = self._classifier
+        if callable(getattr(clf, "forest_tables", None)):
+            return clf.forest_tables()
+        if is_sklearn_trees(clf):
+            if getattr(self, "_forest", None) is None:
+                self._forest = ForestTables.from_sklearn(clf)
+            return self._forest
+        raise NotImplementedError(
+            f"{type(clf).__name__} is not a tree ensemble the MI355X engine runs")

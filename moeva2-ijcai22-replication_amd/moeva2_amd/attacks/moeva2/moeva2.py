@@ -79,15 +79,28 @@ def locked_empty(shape, dtype=np.float64):
     on MI355X vs ~8 GB/s into fresh pageable memory); unregistered when the array is
     collected (numpy runs weakref callbacks before it frees the data).  If registration
     fails the array is returned pageable (the copies are then staged, still correct)."""
+    import mmap
+
     import torch
 
-    a = np.empty(shape, dtype)
-    if a.nbytes == 0:
-        return a
-    _touch(a)
+    dt = np.dtype(dtype)
+    nbytes = int(np.prod(shape, dtype=np.int64)) * dt.itemsize
+    if nbytes == 0:
+        return np.empty(shape, dt)
+    # whole pages of its own: the registered range starts and ends on a page boundary inside
+    # one allocation, so no page of it is shared with a neighbouring heap object (a small
+    # array lives on the brk heap, and a later pageable host -> device copy of its neighbour
+    # would pin a page that is already page-locked here)
+    page = mmap.PAGESIZE
+    span = -(-nbytes // page) * page
+    raw = np.empty(span + page, np.uint8)
+    off = (-raw.ctypes.data) % page
+    a = raw[off:off + nbytes].view(dt).reshape(shape)
+    _touch(raw)
     cudart = torch.cuda.cudart()
-    if int(cudart.cudaHostRegister(a.ctypes.data, a.nbytes, 0)) == 0:
-        weakref.finalize(a, cudart.cudaHostUnregister, a.ctypes.data)
+    if int(cudart.cudaHostRegister(a.ctypes.data, span, 0)) == 0:
+        # on the owner: views of `a` keep `raw` alive, not `a`
+        weakref.finalize(raw, cudart.cudaHostUnregister, a.ctypes.data)
     return a
 
 

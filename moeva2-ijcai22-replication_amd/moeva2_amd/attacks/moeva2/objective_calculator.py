@@ -58,8 +58,8 @@ class ObjectiveCalculator:
         device = int(device)
         objs = self._devs.get(device)
         if objs is None:
-            from ..._native import Mlp, ObjCalc
-            from ...problem import has_device_classifier, has_device_program
+            from ..._native import Forest, Mlp, ObjCalc
+            from ...problem import has_device_classifier, has_device_forest, has_device_program
 
             masks = get_ohe_masks(self._constraints.get_feature_type())
             D = int(self._constraints.get_feature_type().shape[0])
@@ -75,7 +75,9 @@ class ObjectiveCalculator:
                     and has_device_program(self._constraints)):
                 ceng = self._constraints._constraint_engine(device)
             mlp = None
-            if has_device_classifier(self._classifier):
+            if has_device_forest(self._classifier):
+                mlp = Forest(self._classifier.forest_tables(), device=device)
+            elif has_device_classifier(self._classifier):
                 w = self._classifier.dense_weights()
                 mlp = Mlp(w.weights, w.biases, device=device)
             objs = self._devs[device] = (oc, ceng, mlp)

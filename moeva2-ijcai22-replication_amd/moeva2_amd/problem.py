@@ -22,10 +22,21 @@ def has_device_program(constraints) -> bool:
 
 
 def has_device_classifier(classifier) -> bool:
-    """True for Dense(relu)...Dense(softmax) models the engine runs on MFMA; any other
-    ``predict_proba`` model is called on the host."""
+    """True for Dense(relu)...Dense(softmax) models the engine runs on MFMA and for tree
+    ensembles it walks on the device (has_device_forest); any other ``predict_proba`` model
+    is called on the host."""
     try:
         classifier.dense_weights()
+        return True
+    except (NotImplementedError, AttributeError, ValueError):
+        return has_device_forest(classifier)
+
+
+def has_device_forest(classifier) -> bool:
+    """True when the classifier offers forest tables within the engine's limits (a fitted
+    scikit-learn forest / tree classifier, a ForestTables, a ForestModel)."""
+    try:
+        classifier.forest_tables()
         return True
     except (NotImplementedError, AttributeError, ValueError):
         return False
@@ -79,11 +90,14 @@ def get_engine(constraints, classifier, ml_scaler, norm, scale_objectives=True, 
     eng = _ENGINES.get(key)
     if eng is None:
         dev_clf = has_device_classifier(classifier)
-        mlp = classifier.dense_weights() if dev_clf else None
+        forest = classifier.forest_tables() if has_device_forest(classifier) else None
+        mlp = classifier.dense_weights() if dev_clf and forest is None else None
         s, m = scaler_arrays(ml_scaler) if dev_clf else (None, None)
         eng = Engine(build_device_program(constraints, has_device_program(constraints)),
                      mlp.weights if mlp else None, mlp.biases if mlp else None, s, m, norm,
                      scale_objectives, device)
+        if forest is not None:
+            eng.set_forest(forest)
         _ENGINES[key] = (eng, constraints, classifier, ml_scaler)  # keep referents alive
         return eng
     return eng[0]
