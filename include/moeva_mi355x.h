@@ -331,6 +331,11 @@ int mv_attack_population(mv_engine* e, double* genes, double* F, void* stream);
  * the first offsets[B] rows are written).  Any output may be NULL. */
 int mv_attack_front(mv_engine* e, uint8_t* front, int32_t* offsets, double* X, double* Fx,
                     void* stream);
+/* mv_attack_front's kernels on a caller's populations (no engine, as mv_survive): F dev
+ * [B][P][3] and, for X, genes dev [B][P][V]; outputs as mv_attack_front's, front and offsets
+ * required, X / Fx may be NULL.  P <= 1022.  Synchronises the stream before it returns. */
+int mv_front(int32_t B, int32_t P, int32_t V, const double* F, const double* genes,
+             uint8_t* front, int32_t* offsets, double* X, double* Fx, void* stream);
 /* History rows per state = P + (n_gen-1)*O, width 3 (reduced) or 3+C (full): hist [B][rows][w]
  * a device buffer or page-locked host memory (hipHostMalloc / registered: one DMA). */
 int mv_attack_history(mv_engine* e, double* hist, void* stream);

@@ -1068,6 +1068,36 @@ int mv_select_parents(int32_t B, int32_t P, int32_t O, uint64_t seed, int32_t ge
   return MV_OK;
 }
 
+int mv_front(int32_t B, int32_t P, int32_t V, const double* F, const double* genes,
+             uint8_t* front, int32_t* offsets, double* X, double* Fx, void* stream_) {
+  if (B <= 0 || P < 1 || P > SURV_NMAX - 2 || V < 0 || !F || !front || !offsets ||
+      (X && (!genes || V < 1)))
+    return fail(MV_ERR_ARG, "bad mv_front arguments (P <= 1022, X needs genes)");
+  {  // no engine here: every buffer must live on the current device
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    const void* bufs[] = {F, genes, front, offsets, X, Fx};
+    for (const void* q : bufs)
+      if (!on_device(q, dev))
+        return fail(MV_ERR_ARG, "mv_front: a buffer lives on another device than the current one");
+  }
+  // the kernels read members through the attack pool's slot table: here member j is slot j
+  std::vector<int> ident((size_t)B * P);
+  for (size_t t = 0; t < ident.size(); ++t) ident[t] = (int)(t % (size_t)P);
+  int* slot = nullptr;
+  HIPCHK(hipMalloc((void**)&slot, ident.size() * sizeof(int)));
+  hipError_t err = hipMemcpy(slot, ident.data(), ident.size() * sizeof(int), hipMemcpyHostToDevice);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (err == hipSuccess)
+    err = launch_front(B, P, V, V, P, nullptr, nullptr, slot, genes, F, front, offsets, X, Fx,
+                       stream);
+  const hipError_t es = hipStreamSynchronize(stream);  // slot is freed below
+  (void)hipFree(slot);
+  HIPCHK(err);
+  HIPCHK(es);
+  return MV_OK;
+}
+
 int mv_set_profiling(mv_engine* e, int32_t enabled) {
   if (!e) return fail(MV_ERR_ARG, "null engine");
   e->profiling = enabled != 0;

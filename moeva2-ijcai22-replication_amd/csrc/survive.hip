@@ -70,8 +70,10 @@ __global__ void k_gather_pop(int B, int P, int V, int Vr, int S, const int* cmap
 // `opt` of the last generation).  Relation of pareto_operation.py:35-51: i dominates j when
 // F_i < F_j in some objective and F_i > F_j in none; a member is in the front when no other
 // member dominates it (identical rows do not dominate each other).  One workgroup per state,
-// the state's F in LDS (structure of arrays), one member per thread: P <= 1022 compares
-// against broadcast LDS reads.  offsets[b + 1] receives the state's front size.
+// the state's F in LDS (structure of arrays), 256 threads striding over the members, each
+// compared against broadcast LDS reads.  P <= SURV_NMAX - 2 = 1022, the largest pop_size
+// mv_attack_run accepts (P + O <= SURV_NMAX, O >= 2); launch_front refuses more.
+// offsets[b + 1] receives the state's front size.
 __global__ __launch_bounds__(256) void k_front_mask(int P, int S, const int* pop_slot,
                                                      const double* poolF, unsigned char* front,
                                                      int* offsets) {
@@ -262,7 +264,7 @@ hipError_t launch_front(int B, int P, int V, int Vr, int S, const int* cmap, con
                         unsigned char* front, int* offsets, double* X, double* Fx,
                         hipStream_t stream) {
   if (B <= 0) return hipSuccess;
-  if (P < 1 || P > 1024 || !front || !offsets) return hipErrorInvalidValue;
+  if (P < 1 || P > SURV_NMAX - 2 || !front || !offsets) return hipErrorInvalidValue;
   MV_LAUNCH(k_front_mask, dim3(B), dim3(256), (size_t)P * 3 * sizeof(double), stream, P,
                      S, pop_slot, poolF, front, offsets);
   MV_LAUNCH(k_front_scan, dim3(1), dim3(1024), 0, stream, B, offsets);

@@ -42,7 +42,7 @@ EXPORTED = [
     "mv_train_get", "mv_train_get_state", "mv_train_set_state", "mv_train_set_profiling",
     "mv_train_get_kernel_times",
     "mv_forest_create", "mv_forest_destroy", "mv_forest_predict", "mv_engine_set_forest",
-    "mv_objcalc_run_forest",
+    "mv_objcalc_run_forest", "mv_front",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -144,6 +144,7 @@ def lib():
             "mv_attack_run": [vp, C.POINTER(AttackParams), vp],
             "mv_attack_population": [vp, vp, vp, vp],
             "mv_attack_front": [vp, vp, vp, vp, vp, vp],
+            "mv_front": [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp],
             "mv_attack_history": [vp, vp, vp],
             "mv_get_survival_carry": [vp, _i32p, _i32p],
             "mv_set_profiling": [vp, C.c_int32],
@@ -560,6 +561,16 @@ def survive(F, ref_points, n_survive, mu, seed, gen, ideal, worst, extreme, has_
                            seed, gen, _ptr(ideal), _ptr(worst), _ptr(extreme), _ptr(has_extreme),
                            _ptr(survivors), _ptr(rank), _ptr(order), _ptr(n_ranked), _ptr(niche),
                            _ptr(dist), _ptr(nadir), _stream(stream)))
+
+
+def front(F, front, offsets, genes=None, X=None, Fx=None, stream=None):
+    """Non-dominated members of caller-supplied populations (mv_front): F (B, P, 3) and
+    optionally genes (B, P, V) device tensors -> front (B, P) uint8, offsets (B + 1,) int32,
+    X (B * P, V) / Fx (B * P, 3) packed as Engine.attack_front packs them."""
+    B, P, _ = F.shape
+    V = 0 if genes is None else int(genes.shape[2])
+    check(lib().mv_front(B, P, V, _ptr(F), _ptr(genes), _ptr(front), _ptr(offsets), _ptr(X),
+                         _ptr(Fx), _stream(stream)))
 
 
 def select_parents(B, P, O, seed, gen, parents, stream=None):
