@@ -278,6 +278,41 @@ int mv_objcalc_run_forest(mv_objcalc* o, mv_engine* constraints, mv_forest* clas
                           int32_t B, int32_t n, const double* x_init, const double* x,
                           int32_t minimize_class, double* obj, int32_t* range_bad, void* stream);
 
+/* ---- Gradient-boosted tree classifiers (engine extension): scikit-learn's
+ * GradientBoostingClassifier (loss "log_loss") / HistGradientBoostingClassifier predict_proba,
+ * restated in moeva2_amd/models/boost.py.  The tables are mv_forest_desc's with one scalar per
+ * leaf (learning rate included); trees are stage-major: tree t adds its leaf to
+ * raw[t % n_outputs], raw starts at base, in tree order in fp64.  Two classes (n_outputs 1):
+ * p1 = 1 / (1 + E(-raw[0])), p0 = 1 - p1.  More: e[k] = E(raw[k] - max raw),
+ * p[k] = e[k] / ((e[0] + e[1]) + e[2] + ...).  E is mv_det_exp's function on host and device.
+ * Refused with MV_ERR_ARG: everything mv_forest_desc's rules refuse, n_outputs other than 1
+ * for two classes or n_classes for more, n_trees not a multiple of n_outputs, a base or leaf
+ * value that is not finite. */
+typedef struct mv_boost_desc {
+  int32_t n_features;         /* D: the width of a row */
+  int32_t n_classes;          /* 2..8 */
+  int32_t n_outputs;          /* raw scores: 1 when n_classes == 2, else n_classes */
+  int32_t n_trees;            /* stages * n_outputs */
+  int32_t n_leaves;
+  int64_t n_nodes;
+  const int32_t* feature;     /* host [n_nodes] split feature, or -(leaf index) - 1 */
+  const double* threshold;    /* host [n_nodes] */
+  const int32_t* left;        /* host [n_nodes] (unused at a leaf) */
+  const int32_t* right;       /* host [n_nodes] */
+  const int32_t* tree_root;   /* host [n_trees], ascending from 0 */
+  const double* leaf_value;   /* host [n_leaves] fp64 */
+  const double* base;         /* host [n_outputs] fp64 */
+} mv_boost_desc;
+/* A boosted ensemble behind the forest handle: mv_forest_predict, mv_forest_destroy and
+ * mv_objcalc_run_forest take it unchanged and run k_boost. */
+int mv_boost_create(int32_t device, const mv_boost_desc* boost, mv_forest** out);
+/* mv_engine_set_forest for a boosted ensemble: the same preconditions and error codes (an
+ * engine created with model == NULL, no tree ensemble set yet, before mv_set_states:
+ * MV_ERR_STATE otherwise, no device call; boost->n_features must be the problem's D).
+ * mv_get_mlp_kernel then reports 9 (k_boost reading its nodes from global memory) or 10
+ * (k_boost walking a per-workgroup LDS copy: the packed nodes fit 64 KiB). */
+int mv_engine_set_boost(mv_engine* e, const mv_boost_desc* boost);
+
 typedef struct mv_attack_params {
   int32_t n_gen;          /* Moeva2 n_gen (termination "n_gen") */
   int32_t pop_size;       /* P = n_ref_points + n_obj (203 for n_pop 200) */
@@ -398,7 +433,8 @@ int mv_get_row_kernel(mv_engine* e, int32_t* kind);
  * workgroup, any widths), 1 = k_mlp2 reading the child genes (no fp32 ML row is written),
  * 2 = k_mlp2 reading the fp32 ML rows, 4 = k_mlpw (bf16 weights), 5 = k_mlpw32 (fp32 wide
  * nets: 64-row tiles, one activation buffer), 6 / 7 = k_mlpr reading the genes / the fp32 ML
- * rows, 8 = k_forest (a tree ensemble, mv_engine_set_forest), -1 = no device classifier
+ * rows, 8 = k_forest (a tree ensemble, mv_engine_set_forest), 9 / 10 = k_boost (a boosted
+ * ensemble, mv_engine_set_boost) over global memory / LDS, -1 = no device classifier
  * (3, the retired k_mlp2x, is no longer returned).
  * Lets a profiler price the ML-row bytes of the row kernel and the classifier. */
 int mv_get_mlp_kernel(mv_engine* e, int32_t* kind);
@@ -421,6 +457,10 @@ int mv_debug_survival_dump(double* out);
  * arrays.  Replaces np.power in softmax_mutation.py:77-103 (polynomial mutation) and the
  * SBX option's calc_betaq; oracle/device_order.py:det_pow restates it. */
 int mv_det_pow(int64_t n, const double* x, const double* y, double* out);
+/* The engine's exp for the boosted ensembles' sigmoid and softmax (host build of csrc/detmath.h
+ * det_exp2(x, 0.0): fdlibm's exp, the same IEEE operation sequence as k_boost's):
+ * out[i] = E(x[i]) for host arrays.  models/boost.py's specification calls it. */
+int mv_det_exp(int64_t n, const double* x, double* out);
 
 /* ---- C-PGD: the constrained gradient attack (src/attacks/pgd/atk.py:74-163 on ART's PGD
  * loop, src/attacks/pgd/classifier.py:107-332 loss_gradient), whole loop on device.  All

@@ -174,7 +174,9 @@ struct mv_engine {
   int* off_scr = nullptr;
   bool attack_ready = false;
   bool has_model = false;
-  bool has_forest = false;  // mv_engine_set_forest: k_forest is the classifier (p.forest)
+  // mv_engine_set_forest / mv_engine_set_boost: a tree ensemble is the classifier (p.forest:
+  // k_forest, or p.boost: k_boost)
+  bool has_forest = false;
   long long* d_phase = nullptr;  // MV_SURV_PHASES=1: survival phase clocks [B][16]
   long long* d_gphase = nullptr; // MV_GEN_PHASES=1: k_genc clocks [grid][8] (one group)
   bool gphase_mlp = false;        // MV_MLP_PHASES=1: the same buffer holds the classifier's
@@ -824,7 +826,8 @@ int mv_set_states(mv_engine* e, int32_t B, const double* x_init, const double* x
   HIPCHK(hipSetDevice(e->device));
   // a model-less engine (host classifier plugin) evaluates f2 / f3 only: no class check
   const int nout = e->has_model    ? e->p.dims[e->p.n_layers]
-                   : e->has_forest ? e->p.forest.n_classes
+                   : e->has_forest ? (e->p.boost.n_trees > 0 ? e->p.boost.n_classes
+                                                             : e->p.forest.n_classes)
                                    : INT32_MAX;
   for (int b = 0; b < B; ++b)
     if (minimize_class[b] < 0 || minimize_class[b] >= nout)
@@ -1671,6 +1674,12 @@ int mv_det_pow(int64_t n, const double* x, const double* y, double* out) {
   return MV_OK;
 }
 
+int mv_det_exp(int64_t n, const double* x, double* out) {
+  if (n < 0 || (n > 0 && (!x || !out))) return fail(MV_ERR_ARG, "bad mv_det_exp arguments");
+  for (int64_t i = 0; i < n; ++i) out[i] = det_exp2(x[i], 0.0);
+  return MV_OK;
+}
+
 int mv_get_phase_times(mv_engine* e, double* ms, int32_t* n_generations) {
   if (!e || !ms) return fail(MV_ERR_ARG, "null argument");
   double t[4] = {0, 0, 0, 0};
@@ -1985,6 +1994,7 @@ struct mv_forest {
   int device = 0;
   int D = 0;
   DForest f{};
+  DBoost b{};  // mv_boost_create: b.n_trees > 0 and f is empty; the handle runs k_boost
   std::vector<void*> allocs;
   ~mv_forest() {
     (void)hipSetDevice(device);
@@ -2012,6 +2022,95 @@ static hipError_t forest_upload(const mv_forest_desc* d, const std::vector<Fores
   return err;
 }
 
+// ---- gradient-boosted ensembles (boost.hip)
+
+// forest_check's rules on the shared fields, then: n_outputs is 1 exactly when there are two
+// classes (else the class count), n_trees is a multiple of it, base and every leaf value are
+// finite.  No device call.
+static int boost_check(const mv_boost_desc* d, mv_forest_desc* as_forest) {
+  if (!d || !d->base) return fail(MV_ERR_ARG, "boost: null table");
+  mv_forest_desc f{};
+  f.n_features = d->n_features;
+  f.n_classes = d->n_classes;
+  f.n_trees = d->n_trees;
+  f.n_leaves = d->n_leaves;
+  f.n_nodes = d->n_nodes;
+  f.feature = d->feature;
+  f.threshold = d->threshold;
+  f.left = d->left;
+  f.right = d->right;
+  f.tree_root = d->tree_root;
+  f.leaf_value = d->leaf_value;
+  if (const int rc = forest_check(&f)) return rc;
+  if (d->n_outputs != (d->n_classes == 2 ? 1 : d->n_classes))
+    return fail(MV_ERR_ARG, "boost: n_outputs must be 1 for two classes, else n_classes");
+  if (d->n_trees % d->n_outputs)
+    return fail(MV_ERR_ARG, "boost: n_trees must be a multiple of n_outputs");
+  for (int k = 0; k < d->n_outputs; ++k)
+    if (!std::isfinite(d->base[k])) return fail(MV_ERR_ARG, "boost: base must be finite");
+  for (int i = 0; i < d->n_leaves; ++i)
+    if (!std::isfinite(d->leaf_value[i]))
+      return fail(MV_ERR_ARG, "boost: every leaf value must be finite");
+  *as_forest = f;
+  return MV_OK;
+}
+
+// forest_pack's order with the leaf's value in the node (boost.h BoostNode).
+template <class SlotOf>
+static int boost_pack(const mv_forest_desc* f, const mv_boost_desc* d, SlotOf&& slot_of,
+                      std::vector<BoostNode>& nodes, std::vector<int>& roots) {
+  std::vector<ForestNode> fn;
+  if (const int rc = forest_pack(f, slot_of, fn, roots)) return rc;
+  nodes.resize(fn.size());
+  for (size_t i = 0; i < fn.size(); ++i) {
+    nodes[i].slot = fn[i].slot;
+    nodes[i].left = fn[i].left;
+    nodes[i].v = fn[i].slot < 0 ? d->leaf_value[~fn[i].slot] : fn[i].threshold;
+  }
+  return MV_OK;
+}
+
+static hipError_t boost_upload(const mv_boost_desc* d, const std::vector<BoostNode>& nodes,
+                               const std::vector<int>& roots, DBoost& b,
+                               std::vector<void*>& allocs) {
+  hipError_t err = hipSuccess;
+  auto K = [&](auto** dst, const auto* host, size_t n) {
+    if (err != hipSuccess) return;
+    err = upload(dst, host, n);
+    if (err == hipSuccess) allocs.push_back((void*)*dst);
+  };
+  b = DBoost{};
+  K((BoostNode**)&b.nodes, nodes.data(), nodes.size());
+  K((int**)&b.tree_root, roots.data(), roots.size());
+  K((double**)&b.base, d->base, (size_t)d->n_outputs);
+  b.n_nodes = (int)nodes.size();
+  b.n_trees = d->n_trees;
+  b.n_classes = d->n_classes;
+  b.n_outputs = d->n_outputs;
+  return err;
+}
+
+// mv_forest_predict / mv_objcalc_run_forest on either kind of handle
+static hipError_t forest_handle_predict(const mv_forest* f, int rows, const double* x,
+                                        double* proba, hipStream_t st) {
+  if (f->b.n_trees > 0) {
+    BoostArgs ba{};
+    ba.f = f->b;
+    ba.total = rows;
+    ba.D = f->D;
+    ba.x = x;
+    ba.proba = proba;
+    return launch_boost_predict(ba, boost_lds_ok(f->b), st);
+  }
+  ForestArgs fa{};
+  fa.f = f->f;
+  fa.total = rows;
+  fa.D = f->D;
+  fa.x = x;
+  fa.proba = proba;
+  return launch_forest_predict(fa, st);
+}
+
 extern "C" {
 
 int mv_objcalc_run(mv_objcalc* o, mv_engine* e, mv_mlp* m, int32_t B, int32_t n,
@@ -2035,16 +2134,11 @@ int mv_objcalc_run_forest(mv_objcalc* o, mv_engine* e, mv_forest* f, int32_t B, 
   if (!o || !e || !f || B < 0 || n < 0)
     return fail(MV_ERR_ARG, "bad mv_objcalc_run_forest arguments");
   auto predict = [&](int rows, const double* xm, double* proba, hipStream_t st) {
-    ForestArgs fa{};
-    fa.f = f->f;
-    fa.total = rows;
-    fa.D = f->D;
-    fa.x = xm;
-    fa.proba = proba;
-    return launch_forest_predict(fa, st);
+    return forest_handle_predict(f, rows, xm, proba, st);
   };
-  return objcalc_run(o, e, f->D, f->f.n_classes, f->device, predict, B, n, x_init, x,
-                     minimize_class, obj, range_bad, stream_);
+  const int n_out = f->b.n_trees > 0 ? f->b.n_classes : f->f.n_classes;
+  return objcalc_run(o, e, f->D, n_out, f->device, predict, B, n, x_init, x, minimize_class, obj,
+                     range_bad, stream_);
 }
 
 int mv_forest_create(int32_t device, const mv_forest_desc* d, mv_forest** out) {
@@ -2074,13 +2168,7 @@ int mv_forest_predict(mv_forest* f, int32_t n, const double* x, double* proba, v
   if (!on_device(x, f->device) || !on_device(proba, f->device))
     return fail(MV_ERR_ARG, "mv_forest_predict: a buffer lives on another device than the forest");
   HIPCHK(hipSetDevice(f->device));
-  ForestArgs fa{};
-  fa.f = f->f;
-  fa.total = n;
-  fa.D = f->D;
-  fa.x = x;
-  fa.proba = proba;
-  HIPCHK(launch_forest_predict(fa, (hipStream_t)stream));
+  HIPCHK(forest_handle_predict(f, n, x, proba, (hipStream_t)stream));
   return MV_OK;
 }
 
@@ -2089,7 +2177,8 @@ int mv_engine_set_forest(mv_engine* e, const mv_forest_desc* d) {
   // every refusal comes before the first device call
   if (e->has_model)
     return fail(MV_ERR_STATE, "mv_engine_set_forest: the engine was created with an MLP");
-  if (e->has_forest) return fail(MV_ERR_STATE, "mv_engine_set_forest: a forest is already set");
+  if (e->has_forest)
+    return fail(MV_ERR_STATE, "mv_engine_set_forest: a tree ensemble is already set");
   if (e->B > 0)
     return fail(MV_ERR_STATE, "mv_engine_set_forest must come before mv_set_states");
   if (const int rc = forest_check(d)) return rc;
@@ -2108,6 +2197,56 @@ int mv_engine_set_forest(mv_engine* e, const mv_forest_desc* d) {
   const hipError_t err = forest_upload(d, nodes, roots, e->p.forest, e->prob_allocs);
   if (err != hipSuccess) {
     e->p.forest = DForest{};
+    return fail(MV_ERR_HIP, std::string("upload: ") + hipGetErrorString(err));
+  }
+  e->has_forest = true;
+  return MV_OK;
+}
+
+int mv_boost_create(int32_t device, const mv_boost_desc* d, mv_forest** out) {
+  if (!out) return fail(MV_ERR_ARG, "null argument");
+  *out = nullptr;
+  mv_forest_desc fd{};
+  if (const int rc = boost_check(d, &fd)) return rc;
+  std::vector<BoostNode> nodes;
+  std::vector<int> roots;
+  if (const int rc = boost_pack(&fd, d, [](int feat) { return feat; }, nodes, roots)) return rc;
+  HIPCHK(hipSetDevice(device));
+  mv_forest* f = new mv_forest();
+  f->device = device;
+  f->D = d->n_features;
+  const hipError_t err = boost_upload(d, nodes, roots, f->b, f->allocs);
+  if (err != hipSuccess) {
+    delete f;
+    return fail(MV_ERR_HIP, std::string("upload: ") + hipGetErrorString(err));
+  }
+  *out = f;
+  return MV_OK;
+}
+
+int mv_engine_set_boost(mv_engine* e, const mv_boost_desc* d) {
+  if (!e || !d) return fail(MV_ERR_ARG, "null argument");
+  // every refusal comes before the first device call (mv_engine_set_forest's, in its order)
+  if (e->has_model)
+    return fail(MV_ERR_STATE, "mv_engine_set_boost: the engine was created with an MLP");
+  if (e->has_forest)
+    return fail(MV_ERR_STATE, "mv_engine_set_boost: a tree ensemble is already set");
+  if (e->B > 0) return fail(MV_ERR_STATE, "mv_engine_set_boost must come before mv_set_states");
+  mv_forest_desc fd{};
+  if (const int rc = boost_check(d, &fd)) return rc;
+  if (d->n_features != e->p.D) return fail(MV_ERR_ARG, "boost: n_features != D");
+  // a split's value: mv_engine_set_forest's slots
+  std::vector<int> slot(e->p.D);
+  for (int f = 0; f < e->p.D; ++f) slot[f] = e->p.Dm4 + f;
+  for (int j = 0; j < e->hp.Dm; ++j) slot[e->hp.mut[j]] = j;
+  std::vector<BoostNode> nodes;
+  std::vector<int> roots;
+  if (const int rc = boost_pack(&fd, d, [&](int feat) { return slot[feat]; }, nodes, roots))
+    return rc;
+  HIPCHK(hipSetDevice(e->device));
+  const hipError_t err = boost_upload(d, nodes, roots, e->p.boost, e->prob_allocs);
+  if (err != hipSuccess) {
+    e->p.boost = DBoost{};
     return fail(MV_ERR_HIP, std::string("upload: ") + hipGetErrorString(err));
   }
   e->has_forest = true;
@@ -2156,14 +2295,15 @@ int mv_debug_checks(int32_t* record, int32_t* compiled) {
   if (!record) return fail(MV_ERR_ARG, "null record");
   if (compiled) *compiled = MV_CHECKS_ON;
   HIPCHK(hipDeviceSynchronize());
-  int ev[8], sv[8], pg[8], fo[8];
+  int ev[8], sv[8], pg[8], fo[8], bo[8];
   HIPCHK(take_checks_eval(ev));
   HIPCHK(take_checks_survive(sv));
   HIPCHK(take_checks_pgd(pg));
   HIPCHK(take_checks_forest(fo));
-  const int* r = ev[0] ? ev : (sv[0] ? sv : (pg[0] ? pg : fo));
+  HIPCHK(take_checks_boost(bo));
+  const int* r = ev[0] ? ev : (sv[0] ? sv : (pg[0] ? pg : (fo[0] ? fo : bo)));
   for (int k = 0; k < 8; ++k) record[k] = r[k];
-  record[5] = ev[5] + sv[5] + pg[5] + fo[5];
+  record[5] = ev[5] + sv[5] + pg[5] + fo[5] + bo[5];
   return MV_OK;
 }
 

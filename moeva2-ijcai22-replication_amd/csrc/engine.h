@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "boost.h"
 #include "forest.h"
 
 // MV_CLOCKS (development builds: `make variant NAME=clk DEFS=-DMV_CLOCKS=1`): the k_genc /
@@ -142,6 +143,9 @@ struct DProblem {
   // and forest.n_trees > 0.  The row kernels write the fp32 ML rows as they do without a
   // model (xml_direct stays 0) and k_forest reads them
   DForest forest;
+  // ... or a gradient-boosted ensemble (mv_engine_set_boost; boost.h): boost.n_trees > 0, the
+  // same rows and xfix, k_boost reads them
+  DBoost boost;
 };
 
 struct DStates {

@@ -2516,6 +2516,7 @@ static void read_mlp_switches(Switches& s) {
   s.mlp_v1 = std::getenv("MV_MLP_V1") != nullptr;
   s.mlpw = std::getenv("MV_MLPW") != nullptr;
   s.mlpw_off = std::getenv("MV_MLPW_OFF") != nullptr;
+  s.boost_lds_off = env_zero("MV_BOOST_LDS");
 }
 
 // Launches instance K: its first launch allows it the full 160 KiB of dynamic LDS per
@@ -2702,6 +2703,26 @@ hipError_t launch_mlp(const RowsArgs& a, int slot, int hist_row0, hipStream_t st
       fa.hist_w = a.hist_w;
       fa.hist_row0 = hist_row0;
       return launch_forest_rows(fa, stream);
+    }
+    case BOOST_ROWS:
+    case BOOST_ROWS_LDS: {  // boost.hip k_boost over the same rows
+      BoostArgs ba{};
+      ba.f = p.boost;
+      ba.total = a.total;
+      ba.D = p.D;
+      ba.n = a.n;
+      ba.Dm4 = p.Dm4;
+      ba.xml = a.xml;
+      ba.xfix = a.s.xfix;
+      ba.min_class = a.s.min_class;
+      ba.out_map = a.out_map;
+      ba.F = a.F;
+      ba.out_rows = a.out_rows;
+      ba.hist = a.hist;
+      ba.hist_rows = a.hist_rows;
+      ba.hist_w = a.hist_w;
+      ba.hist_row0 = hist_row0;
+      return launch_boost_rows(ba, r.kind == BOOST_ROWS_LDS, stream);
     }
     case MLPR_GENES:
     case MLPR_ROWS: {

@@ -150,6 +150,7 @@ struct Switches {
   bool mlpw_off = false;    // MV_MLPW_OFF set: no k_mlpw
   bool mlpw32_off = false;  // MV_MLPW32=0: keep the 32-row-tile k_mlp
   bool mlp_co_off = false;  // MV_MLP_CO=0: k_mlp2 without the lane-contiguous gene staging
+  bool boost_lds_off = false;  // MV_BOOST_LDS=0: k_boost reads its nodes from L2 (read per launch)
 };
 
 // --- row kernels -------------------------------------------------------------------------
@@ -281,6 +282,8 @@ enum MlpKind {
   MLPR_GENES = 6,   // k_mlpr reading the genes (hidden widths <= 64)
   MLPR_ROWS = 7,    // k_mlpr reading the fp32 ML rows (XML instance)
   FOREST_ROWS = 8,  // k_forest (a tree ensemble) reading the fp32 ML rows and xfix
+  BOOST_ROWS = 9,   // k_boost (a boosted ensemble), the nodes read from global memory (L2)
+  BOOST_ROWS_LDS = 10,  // k_boost walking a per-workgroup LDS copy of the nodes (boost_lds_ok)
 };
 struct MlpRoute {
   int kind;     // MlpKind
@@ -297,6 +300,10 @@ inline MlpRoute mlp_route(const DProblem& p, const Switches& sw) {
   MlpRoute r{};
   if (p.forest.n_trees > 0) {  // the problem carries trees (mv_engine_set_forest: no MLP then)
     r.kind = FOREST_ROWS;
+    return r;
+  }
+  if (p.boost.n_trees > 0) {  // mv_engine_set_boost: no MLP and no forest then
+    r.kind = !sw.boost_lds_off && boost_lds_ok(p.boost) ? BOOST_ROWS_LDS : BOOST_ROWS;
     return r;
   }
   if (p.n_layers == 0) {

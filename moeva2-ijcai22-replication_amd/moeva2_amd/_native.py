@@ -43,6 +43,7 @@ EXPORTED = [
     "mv_train_get_kernel_times",
     "mv_forest_create", "mv_forest_destroy", "mv_forest_predict", "mv_engine_set_forest",
     "mv_objcalc_run_forest", "mv_front",
+    "mv_boost_create", "mv_engine_set_boost", "mv_det_exp",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -85,6 +86,13 @@ class ForestDesc(C.Structure):
                 ("n_leaves", C.c_int32), ("n_nodes", C.c_int64), ("feature", _i32p),
                 ("threshold", _f64p), ("left", _i32p), ("right", _i32p), ("tree_root", _i32p),
                 ("leaf_value", _f64p)]
+
+
+class BoostDesc(C.Structure):
+    _fields_ = [("n_features", C.c_int32), ("n_classes", C.c_int32), ("n_outputs", C.c_int32),
+                ("n_trees", C.c_int32), ("n_leaves", C.c_int32), ("n_nodes", C.c_int64),
+                ("feature", _i32p), ("threshold", _f64p), ("left", _i32p), ("right", _i32p),
+                ("tree_root", _i32p), ("leaf_value", _f64p), ("base", _f64p)]
 
 
 class PgdDesc(C.Structure):
@@ -188,6 +196,9 @@ def lib():
             "mv_engine_set_forest": [vp, C.POINTER(ForestDesc)],
             "mv_objcalc_run_forest": [vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp,
                                       vp, vp],
+            "mv_boost_create": [C.c_int32, C.POINTER(BoostDesc), C.POINTER(vp)],
+            "mv_engine_set_boost": [vp, C.POINTER(BoostDesc)],
+            "mv_det_exp": [C.c_int64, _f64p, _f64p],
         }
         for name, args in sig.items():
             try:
@@ -245,6 +256,16 @@ def det_pow(x, y) -> np.ndarray:
     out = np.empty(x.shape, np.float64)
     f64 = lambda a: a.ctypes.data_as(_f64p)  # noqa: E731
     check(lib().mv_det_pow(x.size, f64(x), f64(y), f64(out)))
+    return out
+
+
+def det_exp(x) -> np.ndarray:
+    """The engine's exp for boosted ensembles (csrc/detmath.h det_exp2(x, 0.0)), host build:
+    elementwise."""
+    x = np.ascontiguousarray(np.asarray(x, np.float64))
+    out = np.empty(x.shape, np.float64)
+    f64 = lambda a: a.ctypes.data_as(_f64p)  # noqa: E731
+    check(lib().mv_det_exp(x.size, f64(x), f64(out)))
     return out
 
 
@@ -381,6 +402,14 @@ class Engine:
         Tables outside the engine's limits raise ValueError."""
         d, keep = _forest_desc(tables)
         _check_forest(lib().mv_engine_set_forest(self._h, C.byref(d)))
+        self.forest = tables
+        self.n_out = tables.n_classes
+
+    def set_boost(self, tables):
+        """Make a boosted ensemble (models.boost.BoostTables) the engine's classifier
+        (mv_engine_set_boost): set_forest's preconditions and errors."""
+        d, keep = _boost_desc(tables)
+        _check_forest(lib().mv_engine_set_boost(self._h, C.byref(d)))
         self.forest = tables
         self.n_out = tables.n_classes
 
@@ -543,10 +572,10 @@ class Engine:
                 "row_kernel": ("k_gen+k_cons", "k_narrow", "k_genc")[rk.value],
                 "mlp_kernel": {-1: None, 0: "k_mlp", 1: "k_mlp2(genes)", 2: "k_mlp2",
                                4: "k_mlpw", 5: "k_mlpw32", 6: "k_mlpr(genes)", 7: "k_mlpr",
-                               8: "k_forest"}[mk.value]}
+                               8: "k_forest", 9: "k_boost", 10: "k_boost(lds)"}[mk.value]}
 
     def mlp_kernel(self) -> int:
-        """mv_get_mlp_kernel's kind (csrc/routes.h MlpKind; 8 = k_forest)."""
+        """mv_get_mlp_kernel's kind (csrc/routes.h MlpKind; 8 = k_forest, 9 / 10 = k_boost)."""
         mk = C.c_int32()
         check(lib().mv_get_mlp_kernel(self._h, C.byref(mk)))
         return int(mk.value)
@@ -666,6 +695,42 @@ class Forest:
 
     def predict(self, x, proba, stream=None):
         check(lib().mv_forest_predict(self._h, x.shape[0], _ptr(x), _ptr(proba), _stream(stream)))
+
+
+def _boost_desc(t):
+    """BoostDesc of a models.boost.BoostTables (and the arrays it points into)."""
+    keep = [np.ascontiguousarray(t.feature, np.int32), np.ascontiguousarray(t.threshold, np.float64),
+            np.ascontiguousarray(t.left, np.int32), np.ascontiguousarray(t.right, np.int32),
+            np.ascontiguousarray(t.tree_root, np.int32),
+            np.ascontiguousarray(t.leaf_value, np.float64).reshape(-1),
+            np.ascontiguousarray(t.base, np.float64).reshape(-1)]
+    d = BoostDesc()
+    d.n_features = int(t.n_features)
+    d.n_classes = int(t.n_classes)
+    d.n_outputs = int(keep[6].shape[0])
+    d.n_trees = int(keep[4].shape[0])
+    d.n_leaves = int(keep[5].shape[0])
+    d.n_nodes = int(keep[0].shape[0])
+    d.feature = keep[0].ctypes.data_as(_i32p)
+    d.threshold = keep[1].ctypes.data_as(_f64p)
+    d.left = keep[2].ctypes.data_as(_i32p)
+    d.right = keep[3].ctypes.data_as(_i32p)
+    d.tree_root = keep[4].ctypes.data_as(_i32p)
+    d.leaf_value = keep[5].ctypes.data_as(_f64p)
+    d.base = keep[6].ctypes.data_as(_f64p)
+    return d, keep
+
+
+class Boost(Forest):
+    """Device boosted ensemble behind the forest handle (mv_boost_create): predict, the
+    destructor and ObjCalc.run are Forest's."""
+
+    def __init__(self, tables, device=0):
+        d, keep = _boost_desc(tables)
+        self._h = C.c_void_p()
+        _check_forest(lib().mv_boost_create(device, C.byref(d), C.byref(self._h)))
+        self.n_out = int(tables.n_classes)
+        self.device = device
 
 
 class ObjCalc:
@@ -914,6 +979,20 @@ def forest_predict_proba(tables, x):
     m = _FORESTS.get(id(tables))
     if m is None:
         m = _FORESTS[id(tables)] = (Forest(tables), tables)
+    m = m[0]
+    xd = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(x), np.float64)).cuda(m.device)
+    out = torch.empty((xd.shape[0], m.n_out), dtype=torch.float64, device=xd.device)
+    m.predict(xd, out)
+    return out.cpu().numpy()
+
+
+def boost_predict_proba(tables, x):
+    """forest_predict_proba for a models.boost.BoostTables."""
+    import torch
+
+    m = _FORESTS.get(id(tables))
+    if m is None:
+        m = _FORESTS[id(tables)] = (Boost(tables), tables)
     m = m[0]
     xd = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(x), np.float64)).cuda(m.device)
     out = torch.empty((xd.shape[0], m.n_out), dtype=torch.float64, device=xd.device)

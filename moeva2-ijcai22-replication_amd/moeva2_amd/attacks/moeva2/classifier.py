@@ -9,12 +9,15 @@ tools/import_reference_data.py is read directly.
 Engine extension: tree ensembles.  A ``.joblib`` file holding a fitted scikit-learn
 RandomForestClassifier / ExtraTreesClassifier / DecisionTreeClassifier, or the ``.npz`` of a
 ``models.forest.ForestTables``, loads as a ``ForestModel`` whose trees run on the device.
+A ``.joblib`` holding a GradientBoostingClassifier (log-loss) / HistGradientBoostingClassifier,
+or the ``.npz`` of a ``models.boost.BoostTables``, loads as a ``BoostModel`` in the same way.
 """
 import os
 
 import numpy as np
 
 from ...io.tf_bundle import DenseMLP, load_dense_mlp
+from ...models.boost import BoostModel, BoostTables, is_sklearn_boost
 from ...models.forest import ForestModel, ForestTables, is_sklearn_trees
 
 
@@ -55,14 +58,18 @@ def load_model(path: str):
         import joblib
 
         model = joblib.load(path)
+        if is_sklearn_boost(model):
+            return BoostModel(BoostTables.from_sklearn(model))
         if not is_sklearn_trees(model):
             raise ValueError(f"{path} holds a {type(model).__name__}; expected a fitted "
-                             "scikit-learn forest or tree classifier")
+                             "scikit-learn forest, tree or gradient-boosting classifier")
         return ForestModel(ForestTables.from_sklearn(model))
     if path.endswith(".npz") or os.path.exists(path + ".npz"):
         d = np.load(path if path.endswith(".npz") else path + ".npz", allow_pickle=False)
         if "forest_tables" in d.files:
             return ForestModel(ForestTables.load(path if path.endswith(".npz") else path + ".npz"))
+        if "boost_tables" in d.files:
+            return BoostModel(BoostTables.load(path if path.endswith(".npz") else path + ".npz"))
         n = sum(1 for k in d.files if k.startswith("W"))
         return DenseMLPModel(DenseMLP([d[f"W{i}"] for i in range(n)],
                                       [d[f"b{i}"] for i in range(n)],
@@ -108,3 +115,17 @@ class Classifier:
             return self._forest
         raise NotImplementedError(
             f"{type(clf).__name__} is not a tree ensemble the MI355X engine runs")
+
+    def boost_tables(self) -> BoostTables:
+        """Tables for the device walk of a boosted ensemble (engine extension): the model is a
+        fitted scikit-learn GradientBoostingClassifier / HistGradientBoostingClassifier, a
+        BoostTables or a BoostModel."""
+        clf = self._classifier
+        if callable(getattr(clf, "boost_tables", None)):
+            return clf.boost_tables()
+        if is_sklearn_boost(clf):
+            if getattr(self, "_boost", None) is None:
+                self._boost = BoostTables.from_sklearn(clf)
+            return self._boost
+        raise NotImplementedError(
+            f"{type(clf).__name__} is not a boosted ensemble the MI355X engine runs")

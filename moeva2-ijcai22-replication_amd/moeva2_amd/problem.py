@@ -23,13 +23,24 @@ def has_device_program(constraints) -> bool:
 
 def has_device_classifier(classifier) -> bool:
     """True for Dense(relu)...Dense(softmax) models the engine runs on MFMA and for tree
-    ensembles it walks on the device (has_device_forest); any other ``predict_proba`` model
-    is called on the host."""
+    ensembles it walks on the device (has_device_forest, has_device_boost); any other
+    ``predict_proba`` model is called on the host."""
     try:
         classifier.dense_weights()
         return True
     except (NotImplementedError, AttributeError, ValueError):
-        return has_device_forest(classifier)
+        return has_device_forest(classifier) or has_device_boost(classifier)
+
+
+def has_device_boost(classifier) -> bool:
+    """True when the classifier offers boost tables within the engine's limits (a fitted
+    scikit-learn GradientBoostingClassifier with the log-loss / HistGradientBoostingClassifier,
+    a BoostTables, a BoostModel)."""
+    try:
+        classifier.boost_tables()
+        return True
+    except (NotImplementedError, AttributeError, ValueError):
+        return False
 
 
 def has_device_forest(classifier) -> bool:
@@ -91,13 +102,17 @@ def get_engine(constraints, classifier, ml_scaler, norm, scale_objectives=True, 
     if eng is None:
         dev_clf = has_device_classifier(classifier)
         forest = classifier.forest_tables() if has_device_forest(classifier) else None
-        mlp = classifier.dense_weights() if dev_clf and forest is None else None
+        boost = classifier.boost_tables() if forest is None and has_device_boost(classifier) \
+            else None
+        mlp = classifier.dense_weights() if dev_clf and forest is None and boost is None else None
         s, m = scaler_arrays(ml_scaler) if dev_clf else (None, None)
         eng = Engine(build_device_program(constraints, has_device_program(constraints)),
                      mlp.weights if mlp else None, mlp.biases if mlp else None, s, m, norm,
                      scale_objectives, device)
         if forest is not None:
             eng.set_forest(forest)
+        if boost is not None:
+            eng.set_boost(boost)
         _ENGINES[key] = (eng, constraints, classifier, ml_scaler)  # keep referents alive
         return eng
     return eng[0]
