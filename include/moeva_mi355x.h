@@ -177,6 +177,16 @@ int mv_survive(int32_t B, int32_t N, int32_t n_survive, const double* F, int32_t
                int32_t* survivors, int32_t* rank, int32_t* order, int32_t* n_ranked,
                int32_t* niche, double* dist, double* nadir, void* stream);
 
+/* mv_survive on a chosen kernel instance: wide is the value mv_attack_run picks from the
+ * number of states for N <= 512 (0: 512 threads per state, mv_survive's; 1: 576; 2: 1024;
+ * anything else is MV_ERR_ARG).  Above N 512 there is one instance and wide is ignored.
+ * Every instance computes the same bits. */
+int mv_survive_wide(int32_t B, int32_t N, int32_t n_survive, const double* F, int32_t R,
+                    const double* ref_points, double mu, uint64_t seed, int32_t gen,
+                    double* ideal, double* worst, double* extreme, int32_t* has_extreme,
+                    int32_t* survivors, int32_t* rank, int32_t* order, int32_t* n_ranked,
+                    int32_t* niche, double* dist, double* nadir, int32_t wide, void* stream);
+
 /* TournamentSelection(comp_by_cv_then_random) for B populations of P: parents dev
  * [B][ceil(O/2)][2] (population positions). */
 int mv_select_parents(int32_t B, int32_t P, int32_t O, uint64_t seed, int32_t gen,

@@ -1003,16 +1003,18 @@ int mv_variation(mv_engine* e, int32_t P, int32_t O, uint64_t seed, int32_t gen,
   return MV_OK;
 }
 
-int mv_survive(int32_t B, int32_t N, int32_t n_survive, const double* F, int32_t R,
-               const double* ref_points, double mu, uint64_t seed, int32_t gen, double* ideal,
-               double* worst, double* extreme, int32_t* has_extreme, int32_t* survivors,
-               int32_t* rank, int32_t* order, int32_t* n_ranked, int32_t* niche, double* dist,
-               double* nadir, void* stream) {
+// mv_survive / mv_survive_wide: wide is SurvArgs.wide (launch_survive ignores it above SURV_NLDS)
+static int survive_direct(int32_t B, int32_t N, int32_t n_survive, const double* F, int32_t R,
+                          const double* ref_points, double mu, uint64_t seed, int32_t gen,
+                          double* ideal, double* worst, double* extreme, int32_t* has_extreme,
+                          int32_t* survivors, int32_t* rank, int32_t* order, int32_t* n_ranked,
+                          int32_t* niche, double* dist, double* nadir, int wide, void* stream) {
   if (B <= 0 || N <= 0 || N > SURV_NMAX || R <= 0 || R > SURV_RMAX || n_survive <= 0 ||
       n_survive > N || !F || !ref_points || !ideal || !worst || !extreme || !has_extreme ||
       !survivors)
     return fail(MV_ERR_ARG, "bad mv_survive arguments (N <= 1024, R <= 640, n_survive <= N)");
-  if (surv_lds_bytes(N, R, 1) > 160 * 1024)
+  const int T = N > SURV_NLDS ? SURV_T_BIG : wide == 2 ? SURV_T_BIG : wide ? SURV_T_MID : SURV_T;
+  if (surv_lds_bytes(N, R, 1, 0, T) > 160 * 1024)
     return fail(MV_ERR_ARG, "mv_survive: N and R too large for the survival LDS workspace");
   {  // no engine here: every buffer must live on the current device
     int dev = 0;
@@ -1043,6 +1045,7 @@ int mv_survive(int32_t B, int32_t N, int32_t n_survive, const double* F, int32_t
   a.niche = niche;
   a.dist = dist;
   a.nadir = nadir;
+  a.wide = wide;
   if (N > SURV_NLDS) {  // dominance bitsets in HBM, stream-ordered scratch
     a.dom_stride = (size_t)N * ((N + 63) / 64);
     HIPCHK(hipMallocAsync((void**)&a.dom_g, (size_t)B * a.dom_stride * 8, (hipStream_t)stream));
@@ -1051,6 +1054,28 @@ int mv_survive(int32_t B, int32_t N, int32_t n_survive, const double* F, int32_t
   if (a.dom_g) HIPCHK(hipFreeAsync(a.dom_g, (hipStream_t)stream));
   HIPCHK(le);
   return MV_OK;
+}
+
+int mv_survive(int32_t B, int32_t N, int32_t n_survive, const double* F, int32_t R,
+               const double* ref_points, double mu, uint64_t seed, int32_t gen, double* ideal,
+               double* worst, double* extreme, int32_t* has_extreme, int32_t* survivors,
+               int32_t* rank, int32_t* order, int32_t* n_ranked, int32_t* niche, double* dist,
+               double* nadir, void* stream) {
+  return survive_direct(B, N, n_survive, F, R, ref_points, mu, seed, gen, ideal, worst, extreme,
+                        has_extreme, survivors, rank, order, n_ranked, niche, dist, nadir, 0,
+                        stream);
+}
+
+int mv_survive_wide(int32_t B, int32_t N, int32_t n_survive, const double* F, int32_t R,
+                    const double* ref_points, double mu, uint64_t seed, int32_t gen,
+                    double* ideal, double* worst, double* extreme, int32_t* has_extreme,
+                    int32_t* survivors, int32_t* rank, int32_t* order, int32_t* n_ranked,
+                    int32_t* niche, double* dist, double* nadir, int32_t wide, void* stream) {
+  if (wide < 0 || wide > 2)
+    return fail(MV_ERR_ARG, "mv_survive_wide: wide must be 0, 1 or 2");
+  return survive_direct(B, N, n_survive, F, R, ref_points, mu, seed, gen, ideal, worst, extreme,
+                        has_extreme, survivors, rank, order, n_ranked, niche, dist, nadir, wide,
+                        stream);
 }
 
 int mv_select_parents(int32_t B, int32_t P, int32_t O, uint64_t seed, int32_t gen,

@@ -1041,7 +1041,12 @@ __device__ __forceinline__ void survive_state(const SurvArgs& a, const int b, co
   }
 
   // ---- aspiration reference directions (normalised), R points + 3 extreme axes
+  // nan_dir: some direction is NaN (a zero-width nadir component under a reference point, a
+  // NaN ideal point).  np.argmin then returns the first such direction for every row, which
+  // the association's fmin pre-filter would skip: every row takes the exact pass.
+  bool nan_dir;
   {
+    int nan_u = 0;
     const double nv = 1.0 / sqrt(3.0);
     const double asp = a.mu * (1.0 / 3.0);
     for (int r = tid; r < RN; r += T) {
@@ -1072,12 +1077,13 @@ __device__ __forceinline__ void survive_state(const SurvArgs& a, const int b, co
       const double nrm = sqrt((res[0] * res[0] + res[1] * res[1]) + res[2] * res[2]);
       for (int k = 0; k < 3; ++k) L.U[r * 3 + k] = res[k] / nrm;
       L.Uf[r] = make_double4(L.U[r * 3], L.U[r * 3 + 1], L.U[r * 3 + 2], 0.0);
+      for (int k = 0; k < 3; ++k) nan_u |= L.U[r * 3 + k] != L.U[r * 3 + k] ? 1 : 0;
     }
     if (tid == 0) {
       L.iscal[15] = 0;
       L.iscal[13] = 0;  // ranked offspring to associate (reuse)
     }
-    __syncthreads();
+    nan_dir = __syncthreads_or(nan_u) != 0;
   }
   PHASE(5)
 
@@ -1119,8 +1125,9 @@ __device__ __forceinline__ void survive_state(const SurvArgs& a, const int b, co
       const int m = L.I[p];
       double Nn[3];
       for (int k = 0; k < 3; ++k) Nn[k] = (L.F[m * 3 + k] - ideal[k]) / den[k];
-      if (Nn[0] == 0.0 && Nn[1] == 0.0 && Nn[2] == 0.0 && !signbit(Nn[0]) && !signbit(Nn[1]) &&
-          !signbit(Nn[2])) {  // at the ideal point: every distance is exactly +0 (both lanes)
+      if (!nan_dir && Nn[0] == 0.0 && Nn[1] == 0.0 && Nn[2] == 0.0 && !signbit(Nn[0]) &&
+          !signbit(Nn[1]) && !signbit(Nn[2])) {  // at the ideal point: every distance is
+                                                 // exactly +0 (both lanes)
         if (!hf) {
           L.niche[p] = 0;
           L.dist[p] = 0.0;
@@ -1160,7 +1167,7 @@ __device__ __forceinline__ void survive_state(const SurvArgs& a, const int b, co
       double best = __builtin_fmin(__builtin_fmin(b0, b1), __builtin_fmin(b2, b3));
       best = __builtin_fmin(best, dpp_f64<0xB1>(best));  // the pair's other lane (DPP xor 1)
       const double lim = best + 1e-14 * (nn + best);
-      if (lim < __builtin_inf()) {  // false on NaN / inf (the same in both lanes)
+      if (lim < __builtin_inf() && !nan_dir) {  // false on NaN / inf (the same in both lanes)
         double bd = __builtin_inf();
         int bj = 0;
         auto cand = [&](int j) {  // exact fp64 distance, np.argmin order
@@ -1206,7 +1213,10 @@ __device__ __forceinline__ void survive_state(const SurvArgs& a, const int b, co
             if (odd && d2f(RN - 1) <= lim) hit(RN - 1);
           }
         }
-        const bool ovf = nc > 4 || dpp_i32<0xB1>(nc) > 4;
+        // the other lane's count read by every lane: under a short-circuit `nc > 4 || ...` the
+        // lanes with nc > 4 sit out the DPP, and their partners read 0 from them
+        const int onc = dpp_i32<0xB1>(nc);
+        const bool ovf = nc > 4 || onc > 4;
         if (!ovf) {
           if (nc > 0) cand(c0);
           if (nc > 1) cand(c1);

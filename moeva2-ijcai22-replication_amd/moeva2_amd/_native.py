@@ -42,7 +42,7 @@ EXPORTED = [
     "mv_train_get", "mv_train_get_state", "mv_train_set_state", "mv_train_set_profiling",
     "mv_train_get_kernel_times",
     "mv_forest_create", "mv_forest_destroy", "mv_forest_predict", "mv_engine_set_forest",
-    "mv_objcalc_run_forest", "mv_front",
+    "mv_objcalc_run_forest", "mv_front", "mv_survive_wide",
     "mv_boost_create", "mv_engine_set_boost", "mv_det_exp",
 ]
 
@@ -147,6 +147,9 @@ def lib():
             "mv_constraints": [vp, C.c_int32, vp, vp, vp],
             "mv_survive": [C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_double,
                            C.c_uint64, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+            "mv_survive_wide": [C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.c_double,
+                                C.c_uint64, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                C.c_int32, vp],
             "mv_select_parents": [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, vp, vp],
             "mv_variation": [vp, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, vp, vp, vp, vp],
             "mv_attack_run": [vp, C.POINTER(AttackParams), vp],
@@ -583,13 +586,24 @@ class Engine:
 
 def survive(F, ref_points, n_survive, mu, seed, gen, ideal, worst, extreme, has_extreme,
             survivors, rank=None, order=None, n_ranked=None, niche=None, dist=None, nadir=None,
-            stream=None):
-    """Batched R-NSGA-III survival on device tensors (see mv_survive)."""
+            stream=None, wide=None):
+    """Batched R-NSGA-III survival on device tensors (see mv_survive).  wide (0, 1, 2) picks
+    the kernel instance for N <= 512 as an attack does from its number of states
+    (mv_survive_wide; None: mv_survive, which is wide 0); every instance computes the same
+    bits."""
     B, N, _ = F.shape
-    check(lib().mv_survive(B, N, n_survive, _ptr(F), ref_points.shape[0], _ptr(ref_points), mu,
-                           seed, gen, _ptr(ideal), _ptr(worst), _ptr(extreme), _ptr(has_extreme),
-                           _ptr(survivors), _ptr(rank), _ptr(order), _ptr(n_ranked), _ptr(niche),
-                           _ptr(dist), _ptr(nadir), _stream(stream)))
+    if wide is None:
+        check(lib().mv_survive(B, N, n_survive, _ptr(F), ref_points.shape[0], _ptr(ref_points),
+                               mu, seed, gen, _ptr(ideal), _ptr(worst), _ptr(extreme),
+                               _ptr(has_extreme), _ptr(survivors), _ptr(rank), _ptr(order),
+                               _ptr(n_ranked), _ptr(niche), _ptr(dist), _ptr(nadir),
+                               _stream(stream)))
+        return
+    check(lib().mv_survive_wide(B, N, n_survive, _ptr(F), ref_points.shape[0], _ptr(ref_points),
+                                mu, seed, gen, _ptr(ideal), _ptr(worst), _ptr(extreme),
+                                _ptr(has_extreme), _ptr(survivors), _ptr(rank), _ptr(order),
+                                _ptr(n_ranked), _ptr(niche), _ptr(dist), _ptr(nadir), wide,
+                                _stream(stream)))
 
 
 def front(F, front, offsets, genes=None, X=None, Fx=None, stream=None):
