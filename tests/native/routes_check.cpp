@@ -138,6 +138,28 @@ static const Synth kSynth[] = {
     {"k_odd", 143, 200, 143, 80, 1, 0, 0, 1, 0},
     {"k_few", 3, 200, 3, 80, 1, 0, 0, 1, 0},
     {"k_mixed", 160, 200, 160, 80, 1, 0, 0, 1, 0},
+    // MV_OP_EXPR columns (full_ops 2): k_gen + k_consx<IDENT, NT> at every vary_nt edge
+    {"x64", 64, 64, 64, 40, 1, 2, 0, 0, 0},
+    {"x65", 65, 65, 65, 40, 1, 2, 0, 0, 0},
+    {"x65/sbx", 65, 65, 65, 40, 1, 2, 0, 0, 1},
+    {"x128", 128, 128, 128, 70, 1, 2, 0, 0, 0},
+    {"x129", 129, 129, 129, 70, 1, 2, 0, 0, 0},
+    {"x256", 256, 256, 256, 100, 1, 2, 0, 0, 0},
+    {"x257", 257, 257, 257, 100, 1, 2, 0, 0, 0},
+    {"x512", 512, 512, 512, 150, 1, 2, 0, 0, 0},
+    {"x513", 513, 513, 513, 150, 1, 2, 0, 0, 0},
+    {"x1024", 1024, 1024, 1024, 300, 1, 2, 0, 0, 0},
+    {"x300c", 300, 300, 300, 400, 1, 2, 3, 0, 0},
+    {"xo32d", 32, 32, 65, 64, 0, 2, 0, 0, 0},
+    {"xo100", 100, 100, 150, 70, 0, 2, 0, 0, 0},
+    {"xo100/sbx", 100, 100, 150, 70, 0, 2, 0, 0, 1},
+    {"xo300f", 300, 300, 330, 100, 0, 2, 0, 0, 0},
+    {"xo520", 520, 520, 600, 150, 0, 2, 0, 0, 0},
+    {"xn8f", 8, 8, 13, 8, 0, 2, 0, 0, 0},
+    {"xk_last", 199, 200, 199, 80, 1, 2, 0, 0, 0},
+    {"xk_odd", 143, 200, 143, 80, 1, 2, 0, 0, 0},
+    {"xk_few", 3, 200, 3, 80, 1, 2, 0, 0, 0},
+    {"xk_mixed", 160, 200, 160, 80, 1, 2, 0, 0, 0},
 };
 static void synth(const Synth& s) {
   DProblem p = problem(2048, s.V, s.Dm, s.C, s.ident != 0, s.full_ops, {32, 16, 2});

@@ -23,6 +23,11 @@ so a ratio's denominator is >= 1 inside the bounds; every seventh plain feature 
 ``dynamic`` lower bound (the input's value); the compact cases fix genes by ``dynamic`` on both
 sides.  The classifier is a fixed-seed Dense D-32-16-2 net with non-zero biases, the ML scaler
 has scale != 1 and min != 0.
+
+``Case.expr`` ("all" / "mixed") restates the selected columns as MV_OP_EXPR expressions in
+``device_program()`` (``op_expression``: the way moeva2_amd/examples/generic.py writes the
+shipped programs); ``eval_ops`` stays the statement of the values, and ``Synth.codes`` holds 16
+for the restated columns, so the engine-order oracle sums f3 in the engine's lane order.
 """
 import dataclasses
 import os
@@ -54,6 +59,9 @@ class Case:
     all_int: bool = False
     sbx: bool = False                  # run a second time with crossover="sbx"
     planovf: bool = False              # also run under the plan-overflow build
+    expr: str = ""                     # "all": every column restated as an MV_OP_EXPR expression;
+    #                                    "mixed": the columns c % 3 == 2 (ABS_SUMDIFF stays dedicated)
+    seed: int = 0                      # the attack's seed where the common one does not do (0)
     # what the engine is expected to run (csrc/routes.h; pinned by tests/test_routes_cpu.py)
     row: str = "k_gen+k_cons"
     row_sbx: str = ""                  # with crossover="sbx" (default: the same)
@@ -136,9 +144,55 @@ CASES = [
          mlp="k_mlpr(genes)",
          note="gene 7 fixed in states 0 and 1, free in state 2: stored", **_GENC),
 ]
+# --- MV_OP_EXPR columns: every program with one runs k_gen +
+# k_consx<IDENT, NT>, whatever its shape; the cases sit where vary_nt changes.  The twin of a
+# case is the same Case with expr="" (the dedicated ops; the kernels of the families above).
+_COMPACT_OF = {}
+for _c in [c for c in CASES if c.name in ("k_last", "k_odd", "k_few", "k_mixed")]:
+    _COMPACT_OF["x" + _c.name] = _c.name
+CASES += [
+    Case("x64", 64, C=40, expr="all", mlp="k_mlpr(genes)", note="k_consx<true,1>, every lane used"),
+    Case("x65", 65, C=40, expr="mixed", sbx=True, mlp="k_mlp2(genes)",
+         note="k_consx<true,2>, one gene in the second slab"),
+    Case("x128", 128, C=70, expr="all", mlp="k_mlpr(genes)", note="k_consx<true,2> full"),
+    Case("x129", 129, C=70, expr="mixed", xor=False, mlp="k_mlp2(genes)",
+         note="k_consx<true,4>: the size that goes to k_genc without EXPR"),
+    Case("x256", 256, C=100, expr="all", mlp="k_mlpr(genes)", note="k_consx<true,4> full"),
+    Case("x257", 257, C=100, expr="mixed", mlp="k_mlp2(genes)", note="k_consx<true,8>"),
+    Case("x512", 512, C=150, expr="mixed", mlp="k_mlpr(genes)", note="k_consx<true,8> full"),
+    Case("x513", 513, C=150, expr="all", mlp="k_mlp2(genes)", note="k_consx<true,16>"),
+    Case("x1024", 1024, C=300, expr="mixed", mlp="k_mlpr(genes)",
+         note="k_consx<true,16> at VARY_MAX_V"),
+    Case("x300c", 300, C=400, expr="mixed", xor=False, sumdiff=(1, 64, 65), mlp="k_mlpr(genes)",
+         note="k_consx<true,8>; 397 lane ops > 64 OPS_REG = 384: the tail loop with EXPR lanes"),
+    Case("xo32d", 30, ohe=(17, 18), C=64, full=True, expr="mixed", note="k_consx<false,2>"),
+    Case("xo100", 94, ohe=(2, 3, 9, 14, 14, 14), C=70, expr="mixed", sbx=True,
+         note="k_consx<false,4>"),
+    Case("xo300f", 294, ohe=(2, 3, 5, 7, 9, 10), C=100, full=True, install=True, expr="all",
+         note="k_consx<false,8>, the POW column"),
+    Case("xo520", 512, ohe=(11,) * 8, C=150, expr="mixed",
+         note="k_consx<false,16> (256 VGPRs and AGPRs)"),
+    Case("xn8f", 6, ohe=(2, 5), C=8, full=True, expr="all",
+         note="k_consx<false,1> on a shape that is k_narrow without EXPR"),
+] + [dataclasses.replace(CASES[[c.name for c in CASES].index(k)], name=x, expr="mixed",
+                         row="k_gen+k_cons",
+                         # xk_few: under the common attack seed, state 0's 3 stored genes of 200
+                         # are hit by no mutation that survives (found on the oracle alone)
+                         seed=8 if x == "xk_few" else 0,
+                         note="k_consx with a compact gene set: " + k)
+     for x, k in _COMPACT_OF.items()]
 CASES_BY_NAME = {c.name: c for c in CASES}
 NARROW = [c.name for c in CASES if c.row == "k_narrow"]
 COMPACT = [c.name for c in CASES if c.fixed is not None]
+EXPR = [c.name for c in CASES if c.expr]
+# fixed genes of the compact cases (the x cases share their twin's pattern)
+N_FIXED = {"k_slab": 64, "k_last": 1, "k_odd": 57, "k_few": 197, "k_mixed": 40}
+N_FIXED.update({x: N_FIXED[k] for x, k in _COMPACT_OF.items()})
+
+
+def twin(case: Case) -> Case:
+    """The same problem with every column a dedicated op (same name: same seeds, same files)."""
+    return dataclasses.replace(case, expr="")
 
 
 def case_seed(name):
@@ -194,15 +248,61 @@ def eval_ops(ops, x, tol=1e-3):
     return c
 
 
+def restated(mode, ops):
+    """Per column: written as an expression under ``mode`` ("all", "mixed" or "")."""
+    if mode == "all":
+        return [True] * len(ops)
+    if mode == "mixed":
+        return [c % 3 == 2 and o[0] != "ABS_SUMDIFF" for c, o in enumerate(ops)]
+    assert mode == "", mode
+    return [False] * len(ops)
+
+
+def op_expression(name, a, k):
+    """One op as an expression, written as moeva2_amd/examples/generic.py writes the shipped
+    programs' columns: the same operands in the same order.  (``eval_ops`` above stays the
+    statement of the values; tests/test_synth_problem_cpu.py holds this one against it.)"""
+    from moeva2_amd.attacks.moeva2.expr import X, absolute, isnan, power, sum_of, where
+    from moeva2_amd.examples.generic import _abs_ratio, _month
+
+    if name == "DIFF":
+        return X[a[0]] - X[a[1]]
+    if name == "RATIO_SAFE":
+        return where(X[a[1]] != 0, X[a[0]] / X[a[1]], 0) - k[0]
+    if name == "XOR_AUG":
+        return absolute(X[a[0]] - ((X[a[1]] >= k[0]) ^ (X[a[2]] >= k[1])))
+    if name == "ABS_SUMDIFF":
+        return absolute(sum_of(a[0]) - sum_of(a[1]))
+    if name == "LCLD_TERM":
+        return absolute((36 - X[a[0]]) * (60 - X[a[0]]))
+    if name == "ABS_RATIO":
+        return _abs_ratio(*a)
+    if name == "MONTHDIFF":
+        return absolute(X[a[0]] - (_month(X[a[1]]) - _month(X[a[2]])))
+    if name == "RATIO_MASKED":
+        ratio = X[a[1]] / X[a[2]]
+        masked = where((X[a[2]] == 0) | (ratio == float("inf")) | isnan(ratio), -1, ratio)
+        return absolute(X[a[0]] - masked)
+    if name == "LCLD_INSTALL":
+        growth = power(1 + X[a[2]] / 1200, X[a[1]])
+        installment = ((X[a[0]] * (X[a[2]] / 1200)) * growth) / (growth - 1)
+        return absolute(X[a[3]] - installment) - k[0]
+    raise ValueError(name)
+
+
 class SynthConstraints(TabularConstraints):
-    def __init__(self, feature_path, constraints_path, ops):
+    def __init__(self, feature_path, constraints_path, ops, expr=""):
         super().__init__(feature_path, constraints_path)
         self._ops = list(ops)
+        self._expr = restated(expr, self._ops)
 
     def device_program(self) -> ConstraintProgram:
         prog = ConstraintProgram()
-        for name, a, k in self._ops:
-            if name == "ABS_SUMDIFF":
+        D = int(self._feature_type.shape[0])
+        for (name, a, k), x in zip(self._ops, self._expr):
+            if x:
+                prog.add_expr(op_expression(name, a, k), D)
+            elif name == "ABS_SUMDIFF":
                 prog.add_sumdiff(list(a[0]), list(a[1]))
             else:
                 prog.add(name, a, k)
@@ -422,7 +522,9 @@ class Synth:
                 fmax[f] = repr(float(np.ceil(X[:, f].max()) + 1.0))
         self.types, self.mutable, self.fmin, self.fmax = tcol, mcol, fmin, fmax
         self.X, self.ops = X, ops
-        self.codes = np.array([OP[o[0]] for o in ops], np.int32)
+        self.restated = np.array(restated(case.expr, ops), bool)
+        self.codes = np.where(self.restated, OP["EXPR"],
+                              np.array([OP[o[0]] for o in ops])).astype(np.int32)
         self.plain_feat, self.is_int, self.term = plain_feat, is_int, term
         self.lay = mo.make_layout(mcol, tcol)
         srng = np.random.default_rng(case_seed(case.name) + 500)
@@ -438,8 +540,18 @@ class Synth:
                 fh.write(f"f{f},{tcol[f]},{bool(mcol[f])},{fmin[f]},{fmax[f]}\n")
         with open(cpath, "w") as fh:
             fh.write("min,max\n" + "0.0,1.0\n" * case.C)
-        self.constraints = SynthConstraints(fpath, cpath, ops)
+        self.constraints = SynthConstraints(fpath, cpath, ops, case.expr)
         self.probs = [self.problem(X[s]) for s in range(B)]
+
+    def expressions(self):
+        """{column: expression} of the restated columns."""
+        return {c: op_expression(*self.ops[c]) for c in np.where(self.restated)[0]}
+
+    def pool_parity(self):
+        """(caller pool entries + code words) & 1: whether the engine pads one word in front
+        of the constants it appends to the index pool (api.cpp)."""
+        prog = self.constraints.device_program()
+        return (len(prog.pool) + len(prog.expr_code)) & 1
 
     def problem(self, x_init):
         return mo.make_problem(self.lay, x_init, self.fmin, self.fmax, self.ml, self.W, self.bs,
@@ -495,10 +607,14 @@ def engine_shape(case: Case, sy: Synth, fixed=None):
     csrc/api.cpp build_problem derives them (``fixed``: the compact layout's feature mask)."""
     nfix = 0 if fixed is None else int(np.asarray(fixed).sum())
     V, Dm = case.V - nfix, case.Dm - nfix
-    lane = [o[0] for o in sy.ops if o[0] != "ABS_SUMDIFF"]
+    names = ["EXPR" if x else o[0] for o, x in zip(sy.ops, sy.restated)]
+    lane = [o for o in names if o != "ABS_SUMDIFF"]
     full = any(o in ("LCLD_INSTALL", "LCLD_TERM", "ABS_RATIO", "MONTHDIFF", "RATIO_MASKED")
                for o in lane)
+    if "EXPR" in lane:  # an EXPR column: the interpreter instances
+        full = 2
     slim = (case.ident and len(lane) <= 64 * 6 and Dm + sy.D < 0x4000
             and all(o in ("DIFF", "RATIO_SAFE") for o in lane))
     return dict(V=V, Dm4=(Dm + 15) // 16 * 16, C=case.C, ident=int(case.ident),
-                full_ops=int(full), sd=len(case.sumdiff), compact=int(nfix > 0), slim=int(slim))
+                full_ops=int(full), sd=len(names) - len(lane), compact=int(nfix > 0),
+                slim=int(slim))

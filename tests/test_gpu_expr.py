@@ -1,13 +1,19 @@
 """MV_OP_EXPR on the device: the shipped LCLD / botnet programs written as generic expressions
 equal the dedicated ops bit for bit, every instruction equals its numpy statement, the lane
 and column loops hold at their edge shapes, mv_engine_create refuses malformed bytecode, and
-the generic programs run through mv_evaluate, the attack and the ObjectiveCalculator."""
+the generic programs run through mv_evaluate, the attack and the ObjectiveCalculator.
+k_constraintsx's row load at D on both sides of 64 and of a second lane trip, the constant
+table on both alignment parities, sum_of pools from 0 to 300 entries and the program that just
+fits the LDS (tests/expr_edges.py) close the file.  (The ten k_consx<IDENT, NT> instances are
+pinned by the x cases of tests/test_gpu_row_routes.py.)"""
 import json
 import os
 
 import numpy as np
 import pytest
 
+import expr_edges as ee
+import synth_problem as sp
 from conftest import RES
 from oracle import moeva_oracle as mo
 from oracle.problems import PROJECTS, Project
@@ -368,3 +374,101 @@ def test_objective_calculator_with_generic_botnet_constraints(golden):
                                       d[f"resp{i}"])
     np.testing.assert_array_equal(calc.success_rate_3d(d["x_init"], d["x_attacks"]),
                                   d["success_rate"])
+
+
+# ------------------------------------------------------------------ rows, tables and LDS at their edges
+def bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+@pytest.mark.parametrize("n", [1, 3, 4, 5])  # one row, a partly filled workgroup, a full one,
+@pytest.mark.parametrize("D", [63, 64, 65, 129])  # one row alone in a second workgroup
+def test_constraintsx_rows_of_larger_d(D, n):
+    """k_constraintsx keeps four rows of D doubles per workgroup and loads each with a lane
+    loop: D below, at and above one trip and above two.  G is preset to a sentinel
+    (run_constraints), so a row or column left unwritten shows; the same rows go through
+    k_gen + k_consx<true, NT>."""
+    from moeva2_amd.attacks.moeva2 import expr as E
+
+    exprs = ee.wide_columns(D)
+    x = ee.wide_rows(D, n, 1000 * D + n)
+    g = run_constraints(device_program(ee.program(exprs, D), D), x)
+    np.testing.assert_array_equal(g, E.evaluate_numpy(exprs, x))
+    assert (g > 0).any()
+
+
+def test_constraintsx_on_the_widest_synthetic_program(tmp_path):
+    """x1024's program (D 1326, a third of its 300 columns expressions): mv_constraints on 1, 3,
+    4 and 5 of the rows the row-route case evaluates; the restated columns against
+    evaluate_numpy, the dedicated ones against the ops' numpy statement, bit for bit."""
+    from moeva2_amd._native import Engine
+    from moeva2_amd.attacks.moeva2 import expr as E
+    from moeva2_amd.problem import build_device_program
+
+    sy = sp.build("x1024", tmp_path)
+    genes, _ = sy.eval_genes(np.random.default_rng(5))
+    rows = mo.genetic_to_ml(sy.lay, genes[0], sy.probs[0].x_init)
+    cols = sy.expressions()
+    idx = sorted(cols)
+    rest = np.setdiff1d(np.arange(sy.case.C), idx)
+    eng = Engine(build_device_program(sy.constraints), None, None)
+    assert sy.D == 1326 and len(idx) == 100
+    for n in (1, 3, 4, 5):
+        x = np.ascontiguousarray(rows[7:7 + n])
+        g = torch.full((n, sy.case.C), -7.0, dtype=torch.float64, device="cuda")
+        eng.constraints(torch.as_tensor(x, device="cuda"), g)
+        g = g.cpu().numpy()
+        np.testing.assert_array_equal(g[:, idx], E.evaluate_numpy([cols[c] for c in idx], x))
+        np.testing.assert_array_equal(g[:, rest], sp.eval_ops(sy.ops, x)[:, rest])
+        assert (g > 0).any()
+
+
+@pytest.mark.parametrize("odd", [False, True], ids=["constants-aligned", "constants-padded"])
+def test_constants_come_back_bit_for_bit(odd):
+    """40 constants (-0.0, 5e-324, the largest double, inf, a NaN with a payload among them),
+    each returned by a column of its own through a select; with a five-word column in front the
+    code words are odd in number and the engine pads one word before the table.  tol = -inf:
+    no value here is clamped."""
+    from moeva2_amd.attacks.moeva2 import expr as E
+
+    exprs = ee.constant_columns(odd)
+    prog = ee.program(exprs, 2)
+    assert ee.const_parity(prog) == int(odd)
+    x = np.array([[1.0, 1.0], [2.5, -0.0], [-3.0, 0.25]])
+    g = run_constraints(device_program(prog, 2, tol=-INF), x, check_f3=False)
+    k = ee.constants()
+    np.testing.assert_array_equal(bits(g[:, int(odd):]), np.tile(bits(k), (3, 1)))
+    np.testing.assert_array_equal(bits(g), bits(E.evaluate_numpy(exprs, x, tol=-INF)))
+
+
+def test_sum_of_pools_from_empty_to_300_entries():
+    """Left to right from 0.0 on both sides, over non-integer features: the same bits.  The
+    empty pool gives +0.0, and so does the pool of one feature that is -0.0."""
+    from moeva2_amd.attacks.moeva2 import expr as E
+
+    exprs, pools = ee.sumf_columns()
+    x = ee.sumf_rows()
+    g = run_constraints(device_program(ee.program(exprs, ee.SUMF_D), ee.SUMF_D, tol=-INF), x,
+                        check_f3=False)
+    np.testing.assert_array_equal(bits(g), bits(E.evaluate_numpy(exprs, x, tol=-INF)))
+    assert (bits(g[:, 0]) == 0).all() and (bits(g[:3, -1]) == 0).all()
+
+
+@pytest.mark.parametrize("columns", [ee.LDS_BOUND_COLUMNS],
+                         ids=[f"{ee.LDS_BOUND_COLUMNS}-columns"])
+def test_program_at_the_lds_bound(columns):
+    """The largest program of maximal (256-word) columns over 12 features whose constraint
+    workspace fits the CU's 160 KiB (the count is the header's: tests/test_expr_edges_cpu.py) is
+    accepted and evaluated; one more column is refused when the engine is created."""
+    from moeva2_amd._native import Engine, NativeError
+    from moeva2_amd.attacks.moeva2 import expr as E
+
+    D = ee.LDS_BOUND_D
+    exprs = ee.bound_columns(columns + 1)
+    x = np.round(np.random.default_rng(12).uniform(-2, 2, size=(5, D)), 3) + 0.0625
+    g = run_constraints(device_program(ee.program(exprs[:-1], D), D), x)
+    ref = E.evaluate_numpy(exprs[:-1], x)
+    np.testing.assert_array_equal(g, ref)
+    assert len({tuple(c) for c in g.T}) == columns and (g > 0).all()
+    with pytest.raises(NativeError, match="error 1: .*too large"):
+        Engine(device_program(ee.program(exprs, D), D), None, None)

@@ -18,7 +18,13 @@ Per case, on 3 states:
   d. a 5-generation attack (P 23, O 10, full history): final genes, F and every history
      column bit-identical to the oracle's engine-order attack (f3 / G at 1e-14 for the one
      case with an LCLD_INSTALL column, whose pow is the device library's);
-  e. narrow cases: the same attack under MV_NARROW=0 is bit-identical.
+  e. narrow cases: the same attack under MV_NARROW=0 is bit-identical;
+  f. cases with MV_OP_EXPR columns (the x cases: k_gen + k_consx<IDENT, NT>, all ten instances,
+     with all or a third of the columns restated as expressions): the twin -- the same problem
+     with every column a dedicated op, on whichever kernels its shape takes, k_genc from 129
+     genes on -- runs the same attack: populations, f1, f2 and every G column of the history
+     bit-identical, f3 within (C - 1) 2^-53 relative (equal non-negative terms summed in
+     another lane order; DESIGN.md section 7b's guarantee, checked across routes).
 Cases marked so run a second time with crossover="sbx"; c129 and c384 also run under the
 plan-overflow build (tests/native/planovf_synth_run.py) with bit-identical populations."""
 import os
@@ -38,7 +44,7 @@ torch = pytest.importorskip("torch")
 
 # seed 7: every case's population changes in every state within these 5 generations (found on
 # the oracle alone; every state draws the same mutations, and k_few's 3 stored genes of 200 are
-# hit by few of them)
+# hit by few of them; a case whose own ``seed`` is set states its reason in synth_problem.py)
 G_ATT, P_ATT, O_ATT, SEED = 5, 23, 10, 7
 RUNS = [(c.name, "two_point") for c in sp.CASES] + [(c.name, "sbx") for c in sp.CASES if c.sbx]
 
@@ -54,10 +60,11 @@ def built(tmp_path_factory):
     d = tmp_path_factory.mktemp("synth")
     cache = {}
 
-    def get(name):
-        if name not in cache:
-            cache[name] = sp.build(name, d)
-        return cache[name]
+    def get(name, twin=False):
+        if (name, twin) not in cache:
+            case = sp.CASES_BY_NAME[name]
+            cache[name, twin] = sp.build(sp.twin(case) if twin else case, d)
+        return cache[name, twin]
 
     return get
 
@@ -91,7 +98,7 @@ def run_attack(sy, cx, hist=2):
     """The device attack of item d: (engine, genes, F, history) as numpy arrays."""
     eng = engine_for(sy, cx)
     try:
-        eng.attack_run(G_ATT, P_ATT, O_ATT, SEED, ref_dirs(), 0.05, hist)
+        eng.attack_run(G_ATT, P_ATT, O_ATT, sy.case.seed or SEED, ref_dirs(), 0.05, hist)
         V, C = eng.prog.V, eng.prog.C
         g = torch.empty((sp.B, P_ATT, V), dtype=torch.float64, device="cuda")
         F = torch.empty((sp.B, P_ATT, 3), dtype=torch.float64, device="cuda")
@@ -201,8 +208,7 @@ def check_attack(sy, cx):
         np.testing.assert_array_equal(stored, ~fixed[mut])
     else:
         assert stored.all() and not fixed.any()
-    assert (~stored).sum() == {"k_slab": 64, "k_last": 1, "k_odd": 57, "k_few": 197,
-                               "k_mixed": 40}.get(case.name, 0)
+    assert (~stored).sum() == sp.N_FIXED.get(case.name, 0)
 
     def ev(prob, genes, return_g=False):
         return do.evaluate_device_order(prob, genes, sy.codes, return_g,
@@ -212,7 +218,8 @@ def check_attack(sy, cx):
     worst = 0.0
     for b, prob in enumerate(sy.probs):
         what = f"{case.name} attack {cx}, state {b}"
-        r = mo.run_attack(prob, ref_dirs(), G_ATT, P_ATT, O_ATT, SEED, save_history="full",
+        r = mo.run_attack(prob, ref_dirs(), G_ATT, P_ATT, O_ATT, case.seed or SEED,
+                          save_history="full",
                           crossover_kind=cx, evaluate_fn=ev, pow_fn=do.det_pow)
         np.testing.assert_array_equal(g[b], r.pop_X, err_msg=what)
         np.testing.assert_array_equal(F[b, :, :2], r.pop_F[:, :2], err_msg=what)
@@ -231,19 +238,35 @@ def check_attack(sy, cx):
     return (g, F, h), worst
 
 
+def check_twin(sy, tw, dev):
+    """Item f: ``dev`` = (genes, F, history) of the attack with EXPR columns."""
+    g, F, h = dev
+    eng, g2, F2, h2 = run_attack(tw, "two_point")
+    what = f"{sy.case.name} against its all-dedicated twin"
+    assert eng.prog.C == sy.case.C and (np.asarray(tw.codes) != 16).all()
+    np.testing.assert_array_equal(g, g2, err_msg=what)
+    np.testing.assert_array_equal(F[..., :2], F2[..., :2], err_msg=what)
+    np.testing.assert_array_equal(h[..., :2], h2[..., :2], err_msg=what)
+    np.testing.assert_array_equal(h[..., 3:], h2[..., 3:], err_msg=what)
+    rtol = (sy.case.C - 1) * 2.0 ** -53
+    np.testing.assert_allclose(F[..., 2], F2[..., 2], rtol=rtol, atol=0, err_msg=what)
+    np.testing.assert_allclose(h[..., 2], h2[..., 2], rtol=rtol, atol=0, err_msg=what)
+    return eng.kernel_times()["row_kernel"]
+
+
 @pytest.mark.parametrize("name,cx", RUNS, ids=[f"{n}-{c}" for n, c in RUNS])
 def test_row_route(built, monkeypatch, name, cx):
     from moeva2_amd._native import NativeError
 
     try:
-        _row_route(built(name), monkeypatch, name, cx)
+        _row_route(built(name), monkeypatch, name, cx, built)
     except NativeError as e:
         if "error 2" in str(e):  # MV_ERR_HIP: start nothing more on a device that faulted
             pytest.exit(f"{name} {cx}: HIP runtime error, session ended: {e}", returncode=3)
         raise
 
 
-def _row_route(sy, monkeypatch, name, cx):
+def _row_route(sy, monkeypatch, name, cx, built):
     case = sy.case
     monkeypatch.delenv("MV_NARROW", raising=False)
     eng = engine_for(sy, cx)
@@ -262,7 +285,10 @@ def _row_route(sy, monkeypatch, name, cx):
         np.testing.assert_array_equal(dev[0], g0)
         np.testing.assert_array_equal(dev[1], F0)
         np.testing.assert_array_equal(dev[2], h0)
-    print(f"{name} {cx} ({case.note}): max |f1 - fp64 forward| {max(worst, w2):.3e}")
+    twin = ""
+    if case.expr and cx == "two_point":  # f. the same program as dedicated ops
+        twin = ", twin on " + check_twin(sy, built(name, twin=True), dev)
+    print(f"{name} {cx} ({case.note}{twin}): max |f1 - fp64 forward| {max(worst, w2):.3e}")
 
 
 PLANOVF_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.pardir,

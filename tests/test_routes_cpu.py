@@ -25,6 +25,8 @@ problem -- stored genes V, Dm4, C, i(dent), f(ull_ops), sd = ABS_SUMDIFF columns
 s(lim), x = SBX -- and mlp= the classifier kind under the cases' D-32-16-2 net: they pin the
 NT / NV / FULL / SLIM instance the kind reported on the GPU does not show
 (tests/test_synth_problem_cpu.py checks each line against the shape the builder makes).
+The x cases carry MV_OP_EXPR columns (f2): cons=3 with nt / ident is the k_consx<IDENT, NT>
+instance, all ten of them.
 """
 import os
 import shutil
@@ -169,6 +171,27 @@ row synth k_last V199 Dm4 208 C80 i1 f0 sd0 c1 s1 x0 kind=2 nt=4 ident=1 sbx=0 s
 row synth k_odd V143 Dm4 144 C80 i1 f0 sd0 c1 s1 x0 kind=2 nt=4 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=1
 row synth k_few V3 Dm4 16 C80 i1 f0 sd0 c1 s1 x0 kind=0 nt=1 ident=1 sbx=0 slim=0 cons=1 nv=0 full=0 need_plan=0 plan_missing=0 mlp=1
 row synth k_mixed V160 Dm4 160 C80 i1 f0 sd0 c1 s1 x0 kind=2 nt=4 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0 mlp=6
+row synth x64 V64 Dm4 64 C40 i1 f2 sd0 c0 s0 x0 kind=0 nt=1 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=6
+row synth x65 V65 Dm4 80 C40 i1 f2 sd0 c0 s0 x0 kind=0 nt=2 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=1
+row synth x65/sbx V65 Dm4 80 C40 i1 f2 sd0 c0 s0 x1 kind=0 nt=2 ident=1 sbx=1 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=1
+row synth x128 V128 Dm4 128 C70 i1 f2 sd0 c0 s0 x0 kind=0 nt=2 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=6
+row synth x129 V129 Dm4 144 C70 i1 f2 sd0 c0 s0 x0 kind=0 nt=4 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=1
+row synth x256 V256 Dm4 256 C100 i1 f2 sd0 c0 s0 x0 kind=0 nt=4 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=6
+row synth x257 V257 Dm4 272 C100 i1 f2 sd0 c0 s0 x0 kind=0 nt=8 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=1
+row synth x512 V512 Dm4 512 C150 i1 f2 sd0 c0 s0 x0 kind=0 nt=8 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=6
+row synth x513 V513 Dm4 528 C150 i1 f2 sd0 c0 s0 x0 kind=0 nt=16 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=1
+row synth x1024 V1024 Dm4 1024 C300 i1 f2 sd0 c0 s0 x0 kind=0 nt=16 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=6
+row synth x300c V300 Dm4 304 C400 i1 f2 sd3 c0 s0 x0 kind=0 nt=8 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=6
+row synth xo32d V32 Dm4 80 C64 i0 f2 sd0 c0 s0 x0 kind=0 nt=2 ident=0 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=7
+row synth xo100 V100 Dm4 160 C70 i0 f2 sd0 c0 s0 x0 kind=0 nt=4 ident=0 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=7
+row synth xo100/sbx V100 Dm4 160 C70 i0 f2 sd0 c0 s0 x1 kind=0 nt=4 ident=0 sbx=1 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=7
+row synth xo300f V300 Dm4 336 C100 i0 f2 sd0 c0 s0 x0 kind=0 nt=8 ident=0 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=7
+row synth xo520 V520 Dm4 608 C150 i0 f2 sd0 c0 s0 x0 kind=0 nt=16 ident=0 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=7
+row synth xn8f V8 Dm4 16 C8 i0 f2 sd0 c0 s0 x0 kind=0 nt=1 ident=0 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=7
+row synth xk_last V199 Dm4 208 C80 i1 f2 sd0 c1 s0 x0 kind=0 nt=4 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=1
+row synth xk_odd V143 Dm4 144 C80 i1 f2 sd0 c1 s0 x0 kind=0 nt=4 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=1
+row synth xk_few V3 Dm4 16 C80 i1 f2 sd0 c1 s0 x0 kind=0 nt=1 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=1
+row synth xk_mixed V160 Dm4 160 C80 i1 f2 sd0 c1 s0 x0 kind=0 nt=4 ident=1 sbx=0 slim=0 cons=3 nv=0 full=0 need_plan=0 plan_missing=0 mlp=6
 """
 
 

@@ -1,7 +1,8 @@
 """The synthetic problems of tests/synth_problem.py, checked without a GPU: the product's
 encoder lays the genes out as the oracle does, the inputs make the constraints bite without
 saturating, the compact cases fix the intended genes, and every case's shape and expected
-kernels are the ones a line of the route table (tests/test_routes_cpu.py) pins."""
+kernels are the ones a line of the route table (tests/test_routes_cpu.py) pins.  For the cases
+with MV_OP_EXPR columns: the restated columns equal ``eval_ops`` bit for bit."""
 import re
 
 import numpy as np
@@ -117,9 +118,8 @@ def test_compact_masks(built, name):
     sy, case = built(name), sp.CASES_BY_NAME[name]
     fixed = do.compact_fixed(sy.lay, sy.probs)
     np.testing.assert_array_equal(fixed, _intended_fixed(case, sy))
-    want = {"k_slab": 64, "k_last": 1, "k_odd": 57, "k_few": 197, "k_mixed": 40}.get(name, 0)
-    assert fixed.sum() == want
-    if name == "k_mixed":  # gene 7: fixed in states 0 and 1 only, so it is stored
+    assert fixed.sum() == sp.N_FIXED.get(name, 0)
+    if name in ("k_mixed", "xk_mixed"):  # gene 7: fixed in states 0 and 1 only, so it is stored
         fx = [do.compact_fixed(sy.lay, [p])[sy.plain_feat[7]] for p in sy.probs]
         assert fx == [True, True, False] and not fixed[sy.plain_feat[7]]
 
@@ -175,4 +175,67 @@ def test_every_instance_family_has_a_line():
     assert any(v[K] == 2 and v[SBX] == 1 for v in L)
     assert any(v[K] == 0 and v[SBX] == 1 and v[ID] == 1 and v[0] <= 8 for v in L)
     assert any(v[K] == 0 and v[SBX] == 1 and v[ID] == 0 for v in L)
-    assert sum(v[6] for v in L) == len(sp.COMPACT) == 5
+    assert sum(v[6] for v in L) == len(sp.COMPACT) == 9
+    for ident in (0, 1):  # k_consx<IDENT, NT>: the ten instances
+        for nt in (1, 2, 4, 8, 16):
+            assert any(v[K] == 0 and v[CONS] == 3 and v[NT] == nt and v[ID] == ident for v in L), \
+                (ident, nt)
+    assert any(v[CONS] == 3 and v[SBX] == 1 and v[ID] == ident for ident in (0, 1) for v in L)
+    assert sum(v[CONS] == 3 and v[6] for v in L) == 4  # ... and with a compact gene set
+
+
+# ------------------------------------------------------------------ MV_OP_EXPR cases
+# (caller pool entries + code words) & 1 per case: odd -> the engine pads one word in front of
+# the constants it appends to the index pool.  Both sides occur.
+POOL_PARITY = {"x64": 0, "x65": 1, "x128": 0, "x129": 0, "x256": 0, "x257": 1, "x512": 0,
+               "x513": 0, "x1024": 0, "x300c": 1, "xo32d": 1, "xo100": 1, "xo300f": 1, "xo520": 0,
+               "xn8f": 0, "xk_last": 1, "xk_odd": 1, "xk_few": 1, "xk_mixed": 1}
+
+
+def test_expr_cases_cover_both_pool_parities():
+    assert set(POOL_PARITY) == set(sp.EXPR) and set(POOL_PARITY.values()) == {0, 1}
+    assert [n for n in sp.EXPR if sp.CASES_BY_NAME[n].expr == "all"]
+    assert [n for n in sp.EXPR if sp.CASES_BY_NAME[n].expr == "mixed"]
+
+
+@pytest.mark.parametrize("name", sp.EXPR)
+def test_restatement_equals_the_ops_bit_for_bit(built, name):
+    """evaluate_numpy of the restated columns against eval_ops -- which stays the statement
+    of the values -- on the rows the GPU case evaluates: the same bits, NaN in the same places
+    (the LCLD_INSTALL column, np.power on both sides, at 1e-14).  And the program's shape:
+    which columns are EXPR, that ABS_SUMDIFF stays dedicated in the mixed mode, and the parity
+    of the words in front of the constants."""
+    from moeva2_amd.attacks.moeva2 import expr as E
+
+    sy, case = built(name), sp.CASES_BY_NAME[name]
+    cols = sy.expressions()
+    idx = sorted(cols)
+    names = [sy.ops[c][0] for c in range(case.C)]
+    if case.expr == "all":
+        assert idx == list(range(case.C))
+    else:
+        assert idx == [c for c in range(case.C) if c % 3 == 2 and names[c] != "ABS_SUMDIFF"]
+        assert {names[c] for c in idx} >= {"DIFF", "RATIO_SAFE"}
+        assert {names[c] for c in range(case.C) if c not in cols} >= {"DIFF", "RATIO_SAFE"}
+    assert (sy.codes[idx] == 16).all() and (np.delete(sy.codes, idx) != 16).all()
+    prog = sy.constraints.device_program()
+    np.testing.assert_array_equal(prog.arrays()[0], sy.codes)
+    assert sy.pool_parity() == POOL_PARITY[name]
+    assert sum(n == "ABS_SUMDIFF" and c not in cols for c, n in enumerate(names)) == \
+        (0 if case.expr == "all" else len(case.sumdiff))
+    genes, _ = sy.eval_genes(np.random.default_rng(sp.case_seed(name) + 1))
+    exact = [c for c in idx if names[c] != "LCLD_INSTALL"]
+    install = [c for c in idx if names[c] == "LCLD_INSTALL"]
+    assert len(install) == int(case.install and case.expr == "all")
+    seen_nan = seen_pos = False
+    for b, prob in enumerate(sy.probs):
+        x = mo.genetic_to_ml(sy.lay, genes[b], prob.x_init)
+        ref = sp.eval_ops(sy.ops, x)
+        got = E.evaluate_numpy([cols[c] for c in idx], x)
+        at = {c: j for j, c in enumerate(idx)}
+        np.testing.assert_array_equal(got[:, [at[c] for c in exact]], ref[:, exact])
+        for c in install:
+            np.testing.assert_allclose(got[:, at[c]], ref[:, c], rtol=1e-14, atol=0)
+        seen_nan |= bool(np.isnan(ref[:, exact]).any())
+        seen_pos |= bool((ref[:, exact] > 0).any())
+    assert seen_pos
