@@ -459,8 +459,12 @@ static int build_problem(const HostProblem& h, const HostModel* hm, const std::v
     p.mlp2 = 1;
     for (int l = 1; l < hm->n_layers; ++l) p.mlp2 &= hm->dims[l] % 16 == 0 && hm->dims[l] <= 128;
     // xml_direct: k_mlp2 builds its layer-0 tiles from the child genes (MV_XML: the fp32
-    // ML rows written by the row kernel + k_mlp2, A/B only)
-    p.xml_direct = p.mlp2 && p.ident && !std::getenv("MV_XML");
+    // ML rows written by the row kernel + k_mlp2, A/B only).  MV_MLP_V1 / MV_MLPW send a narrow
+    // net to k_mlp / k_mlpw, which read the ML rows only: under them the rows are written too
+    // (with xml_direct left set the row kernels wrote none and those kernels classified an
+    // unwritten buffer), so these switches are set before the engine is created, like MV_XML
+    p.xml_direct = p.mlp2 && p.ident && !std::getenv("MV_XML") && !std::getenv("MV_MLP_V1") &&
+                   !std::getenv("MV_MLPW");
     // the same packing feeds k_mlpw32 (fp32 wide nets): every hidden width a multiple of 16
     bool pack16 = true;
     for (int l = 1; l < hm->n_layers; ++l) pack16 &= hm->dims[l] % 16 == 0;

@@ -25,6 +25,11 @@ and the device attack can be compared trajectory for trajectory:
   the last Dense layer only: wave w of 8 keeps the last hidden layer's column tiles w + 8 j
   in registers, lane il chains fmaf over j, the 16 lanes are combined by the
   xor-1,2,4,8 butterfly, the 8 wave partials are added in wave order from 0.f, then the bias.
+  k_mlp (the 32-row-tile fallback; ``kernel="mlp_v1"``) shares the layer-0 bias and walks k in
+  natural ascending order everywhere: dense_mfma issues one v_mfma_f32_16x16x4f32 per
+  kk = 0, 4, 8, ... and each adds k = kk + ka for ka = 0..3 (the software pipeline's steps past
+  K multiply zeros), so a hidden output is one fmaf chain over k = 0..K-1 from 0.f, then
+  + bias and ReLU; last_layer_softmax is one fmaf chain over k from 0.f, then s + b in fp32.
 * f2: each of 64 lanes sums the squared distances of features lane + 64 t in order, the 64
   partial sums are combined by the wave's butterfly (a balanced pairwise tree in lane
   order), then sqrt and the scale (default_problem.py:80-91).
@@ -198,6 +203,14 @@ def _dense_mfma(h, W, K):
     return acc
 
 
+def _dense_seq(h, W, K):
+    """dense_mfma (k_mlp): as _dense_mfma with k = 0..K-1 ascending."""
+    acc = np.zeros((h.shape[0], W.shape[1]), np.float32)
+    for k in range(K):
+        acc = _fma32(h[:, k:k + 1], W[k][None, :], acc)
+    return acc
+
+
 def _mutable(prob, fixed):
     """The engine's mutable features: the layout's, less the compact layout's fixed ones."""
     m = np.asarray(prob.lay.mutable_mask, bool)
@@ -277,10 +290,12 @@ def _last_dense_mlpw32(h, W, cj):
 
 def f1_device_order(prob: "mo.Problem", x_f: np.ndarray, fixed=None,
                     kernel="mlp2") -> np.ndarray:
-    """``kernel``: "mlp2" (k_mlp2 and k_mlpr: the same order) or "mlpw32" (the fp32 wide
-    classifier: the same layer-0 bias and MFMA hidden layers, its own last Dense)."""
-    if kernel not in ("mlp2", "mlpw32"):
-        raise ValueError(f"kernel {kernel!r}: 'mlp2' or 'mlpw32'")
+    """``kernel``: "mlp2" (k_mlp2 and k_mlpr: the same order), "mlpw32" (the fp32 wide
+    classifier: the same layer-0 bias and MFMA hidden layers, its own last Dense) or "mlp_v1"
+    (k_mlp, the 32-row-tile fallback: the same layer-0 bias, every chain in ascending k)."""
+    if kernel not in ("mlp2", "mlpw32", "mlp_v1"):
+        raise ValueError(f"kernel {kernel!r}: 'mlp2', 'mlpw32' or 'mlp_v1'")
+    dense = _dense_seq if kernel == "mlp_v1" else _dense_mfma
     mut = np.where(_mutable(prob, fixed))[0]
     x_ml = x_f if prob.ml_scale is None else mo.minmax_transform(x_f, prob.ml_scale, prob.ml_min)
     Dm = mut.size
@@ -290,14 +305,16 @@ def f1_device_order(prob: "mo.Problem", x_f: np.ndarray, fixed=None,
     W0 = np.zeros((K0, prob.weights[0].shape[1]), np.float32)
     W0[:Dm] = prob.weights[0][mut].astype(np.float32)
     nl = len(prob.weights)
-    h = np.maximum(_dense_mfma(h, W0, K0) + layer0_bias(prob, fixed), np.float32(0))
+    h = np.maximum(dense(h, W0, K0) + layer0_bias(prob, fixed), np.float32(0))
     for l in range(1, nl - 1):
         W = prob.weights[l].astype(np.float32)
-        h = np.maximum(_dense_mfma(h, W, W.shape[0]) + prob.biases[l].astype(np.float32),
+        h = np.maximum(dense(h, W, W.shape[0]) + prob.biases[l].astype(np.float32),
                        np.float32(0))
     W = prob.weights[nl - 1].astype(np.float32)
     if kernel == "mlpw32":
         z = _last_dense_mlpw32(h, W, mlpw32_cj(prob))
+    elif kernel == "mlp_v1":
+        z = _dense_seq(h, W, W.shape[0])
     else:
         z = _last_dense_mlp2(h, W)
     z = z + prob.biases[nl - 1].astype(np.float32)

@@ -2,8 +2,10 @@
 // for hand-filled problems, and vary_rows_per_wg's chunking.  Host-only: no GPU, no library
 // load.  Built and run by tests/test_routes_cpu.py, which holds the expected lines.
 #include <cstdio>
+#include <cstring>
 #include <initializer_list>
 
+#include "kernels.h"
 #include "routes.h"
 using namespace mv;
 
@@ -54,6 +56,12 @@ static DProblem lcld(std::initializer_list<int> net, int V = 15, int full_ops = 
   return problem(47, V, 28, 10, false, full_ops, net);
 }
 
+// MV_XML, MV_MLP_V1, MV_MLPW: mv_engine_create leaves xml_direct 0 (the row kernels write the
+// fp32 ML rows)
+static DProblem rows_written(DProblem p) {
+  p.xml_direct = 0;
+  return p;
+}
 static void mlp(const char* name, const DProblem& p, const Switches& sw = Switches{}) {
   const MlpRoute r = mlp_route(p, sw);
   std::printf("mlp %-34s kind=%d rw=%d no=%d xml=%d cj=%d bf=%d direct=%d co=%d maxct=%d\n", name,
@@ -177,6 +185,38 @@ static void synth(const Synth& s) {
               (int)r.plan_missing, mlp_route(p, Switches{}).kind);
 }
 
+// The classifier-fallback shapes of tests/synth_problem.py MLP_CASES (IDENT, V = Dm plain
+// genes, 12 slim columns) under their own nets, in the fp32 and the bf16 mode and under
+// MV_MLP_V1 (m639t: with MV_MLPR=0) where a GPU case sets it: the k_mlp<MAXCT, BF> instance each one names.
+static void mlp_synth(const char* name, int Dm, std::initializer_list<int> net, bool bf16 = false,
+                      int v1 = 0) {
+  DProblem p = problem(Dm + 14, Dm, Dm, 12, true, 0, net, bf16);
+  p.slim = 1;
+  Switches sw;
+  if (v1) {  // MV_MLP_V1: set at create, where it has the fp32 ML rows written (xml_direct 0)
+    sw.mlp_v1 = true;
+    p.xml_direct = 0;
+    sw.mlpr_off = v1 == 2;  // the case also sets MV_MLPR=0
+  }
+  char nets[64] = "", full[96];
+  for (int h : net) std::snprintf(nets + std::strlen(nets), sizeof nets - std::strlen(nets),
+                                  "%s%d", nets[0] ? "-" : "", h);
+  std::snprintf(full, sizeof full, "synth %s Dm4 %d %s %s%s", name, p.Dm4, nets,
+                bf16 ? "bf16" : "fp32", v1 ? " MV_MLP_V1" : "");
+  mlp(full, p, sw);
+}
+// mv_engine_create's LDS check (api.cpp build_problem: mlp_lds_bytes <= 160 KiB) and the two
+// wide kernels' own budgets, at both sides of each edge
+static void lds(int Dm4, std::initializer_list<int> net) {
+  DProblem p = problem(Dm4 + 14, Dm4, Dm4, 12, true, 0, net);
+  const int nl = p.n_layers;
+  const size_t v1 = mlp_lds_bytes(p.Dm4, max_hidden(p.dims, nl), p.dims[nl - 1], p.dims[nl]);
+  std::printf("lds Dm4 %d", Dm4);
+  for (int h : net) std::printf("-%d", h);
+  std::printf(" k_mlp=%zu create=%s k_mlpw32=%u k_mlpw=%u\n", v1,
+              v1 <= 160 * 1024 ? "ok" : "refused", mlpw32_lds(p).total, mlpw_lds(p).total);
+}
+
 int main() {
   // --- classifier routes, default switches
   mlp("botnet 312-64-64-32-2", botnet({64, 64, 32, 2}, 312));
@@ -224,12 +264,12 @@ int main() {
   s = Switches{}, s.mlpr_rw = 7;
   mlp("MV_MLPR_RW=7 botnet 312-64-64-32-2", botnet({64, 64, 32, 2}, 312), s);
   s = Switches{}, s.mlp_v1 = true;
-  mlp("MV_MLP_V1 botnet hidden 128", botnet({128, 64, 2}), s);
-  mlp("MV_MLP_V1 botnet 312-64-64-32-2", botnet({64, 64, 32, 2}, 312), s);
-  mlp("MV_MLP_V1 bf16 hidden 128", botnet({128, 64, 2}, 432, true), s);
+  mlp("MV_MLP_V1 botnet hidden 128", rows_written(botnet({128, 64, 2})), s);
+  mlp("MV_MLP_V1 botnet 312-64-64-32-2", rows_written(botnet({64, 64, 32, 2}, 312)), s);
+  mlp("MV_MLP_V1 bf16 hidden 128", rows_written(botnet({128, 64, 2}, 432, true)), s);
   s = Switches{}, s.mlpw = true;
-  mlp("MV_MLPW bf16 hidden 64", botnet({64, 64, 32, 2}, 432, true), s);
-  mlp("MV_MLPW fp32 hidden 128", botnet({128, 64, 2}), s);
+  mlp("MV_MLPW bf16 hidden 64", rows_written(botnet({64, 64, 32, 2}, 432, true)), s);
+  mlp("MV_MLPW fp32 hidden 128", rows_written(botnet({128, 64, 2})), s);
   s = Switches{}, s.mlpw_off = true;
   mlp("MV_MLPW_OFF bf16 hidden 256", botnet({256, 128, 2}, 432, true), s);
   mlp("MV_MLPW_OFF bf16 hidden 64", botnet({64, 64, 32, 2}, 432, true), s);
@@ -238,6 +278,33 @@ int main() {
   mlp("MV_MLPW32=0 fp32 hidden 512", botnet({512, 512, 256, 2}), s);
   s = Switches{}, s.mlp_co_off = true;
   mlp("MV_MLP_CO=0 botnet hidden 80", botnet({80, 32, 2}), s);
+
+  // --- the k_mlp fallback's cases and their LDS edges (160 KiB = 163840)
+  mlp_synth("m608w", 608, {512, 512, 2});
+  mlp_synth("m609w", 609, {512, 512, 2});
+  mlp_synth("m609w", 609, {512, 512, 2}, true);
+  mlp_synth("m736w", 736, {512, 272, 3});
+  mlp_synth("m1008w", 1008, {144, 240, 3});
+  mlp_synth("m1008w", 1008, {144, 240, 3}, true);
+  mlp_synth("m640n", 640, {48, 80, 2});
+  mlp_synth("m640n", 640, {48, 80, 2}, false, 1);
+  mlp_synth("m639t", 639, {32, 16, 8});
+  mlp_synth("m639t", 639, {32, 16, 8}, false, 2);
+  mlp("MV_MLP_V1 even Dm 640-32-16-8",
+      rows_written(problem(654, 640, 640, 12, true, 0, {32, 16, 8})),
+      [] { Switches t; t.mlp_v1 = true; return t; }());
+  mlp("bf16 botnet 756-512-512-8", botnet({512, 512, 8}, 432, true));
+  mlp("bf16 botnet 756-512-256-8", botnet({512, 256, 8}, 432, true));
+  lds(608, {512, 512, 2});
+  lds(624, {512, 512, 2});
+  lds(720, {512, 512, 2});
+  lds(736, {512, 512, 2});
+  lds(736, {512, 272, 3});
+  lds(752, {512, 272, 3});
+  lds(1008, {144, 240, 3});
+  lds(1024, {144, 240, 3});
+  lds(432, {512, 512, 8});
+  lds(432, {512, 256, 8});
 
   // --- row routes
   const std::initializer_list<int> net = {64, 64, 32, 2};

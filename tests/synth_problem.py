@@ -21,7 +21,8 @@ shares on the oracle alone).  The mutable operands go round the plain features f
 Bounds lie on a 1/8 grid (any float parser reads them exactly) with every lower bound >= 1,
 so a ratio's denominator is >= 1 inside the bounds; every seventh plain feature has a
 ``dynamic`` lower bound (the input's value); the compact cases fix genes by ``dynamic`` on both
-sides.  The classifier is a fixed-seed Dense D-32-16-2 net with non-zero biases, the ML scaler
+sides.  The classifier is a fixed-seed Dense D-32-16-2 net with non-zero biases (``Case.net``
+gives another one: MLP_CASES, the shapes of the classifier's fallback kernel), the ML scaler
 has scale != 1 and min != 0.
 
 ``Case.expr`` ("all" / "mixed") restates the selected columns as MV_OP_EXPR expressions in
@@ -62,6 +63,8 @@ class Case:
     expr: str = ""                     # "all": every column restated as an MV_OP_EXPR expression;
     #                                    "mixed": the columns c % 3 == 2 (ABS_SUMDIFF stays dedicated)
     seed: int = 0                      # the attack's seed where the common one does not do (0)
+    net: Tuple[int, ...] = ()          # classifier (hidden..., classes); () = the D-32-16-2 net
+    mlp_v1: str = ""                   # the classifier kernel under MV_MLP_V1, where a test runs it
     # what the engine is expected to run (csrc/routes.h; pinned by tests/test_routes_cpu.py)
     row: str = "k_gen+k_cons"
     row_sbx: str = ""                  # with crossover="sbx" (default: the same)
@@ -181,6 +184,35 @@ CASES += [
                          seed=8 if x == "xk_few" else 0,
                          note="k_consx with a compact gene set: " + k)
      for x, k in _COMPACT_OF.items()]
+# --- the classifier's 32-row-tile fallback k_mlp<MAXCT, BF> (tests/test_gpu_mlp_fallback.py,
+# tests/test_gpu_bf16_routes.py): plain mutable features only, few columns, a net of their own.
+# Kept apart from CASES: the row-route tests run every entry of CASES under the D-32-16-2 net.
+# The shapes sit at the LDS edges that tests/native/routes_check.cpp computes ("lds" and "mlp
+# synth" lines of tests/test_routes_cpu.py): a 512-512-2 net's mlpw32_lds passes 160 KiB from
+# Dm4 624 on (a 512-256-2 net's from 640 on: the final layer's weights share the budget), so
+# the pair is 608 | 609 features; mv_engine_create's mlp_lds_bytes check accepts 512-512-2 up
+# to Dm4 720 (736 is refused), 512-272-3 up to 736 and 144-240-3 up to 1008 (1024 is refused:
+# the widest case is 1008 features, not VARY_MAX_V).  m639t has an odd gene count because an even one with hidden
+# widths <= 64 stays on k_mlpr under MV_MLP_V1 (mlpr_ok comes first in mlp_route).
+_MLP = dict(C=12, xor=False, row="k_genc")
+MLP_CASES = [
+    Case("m608w", 608, net=(512, 512, 2), mlp="k_mlpw32",
+         note="k_mlpw32<4>: the near side of the mlpw32_lds guard", **_MLP),
+    Case("m609w", 609, net=(512, 512, 2), sbx=True, mlp="k_mlp",
+         note="k_mlp<8,false>; Dm4 624 (bf16: 19.5 steps of 32, the half step in layer 0)", **_MLP),
+    Case("m736w", 736, net=(512, 272, 3), mlp="k_mlp",
+         note="k_mlp<8,false> at the largest Dm4 this net is accepted at; 32 and 17 column "
+              "tiles, 3 classes", **_MLP),
+    Case("m1008w", 1008, net=(144, 240, 3), mlp="k_mlp",
+         note="k_mlp<4,false> at the largest Dm4 this net is accepted at; 9 and 15 column tiles "
+              "(bf16: K 144, the half step)", **_MLP),
+    Case("m640n", 640, net=(48, 80, 2), mlp="k_mlp2(genes)", mlp_v1="k_mlp",
+         note="MV_MLP_V1: k_mlp<2,false>, U = 8 with K 48 (the kk < K tail); 3 and 5 column tiles",
+         **_MLP),
+    Case("m639t", 639, net=(32, 16, 8), mlp="k_mlp2(genes)", mlp_v1="k_mlp",
+         note="MV_MLP_V1: k_mlp<1,false>, waves 2 and 3 without a column tile, 8 classes", **_MLP),
+]
+MLP_BY_NAME = {c.name: c for c in MLP_CASES}
 CASES_BY_NAME = {c.name: c for c in CASES}
 NARROW = [c.name for c in CASES if c.row == "k_narrow"]
 COMPACT = [c.name for c in CASES if c.fixed is not None]
@@ -196,7 +228,13 @@ def twin(case: Case) -> Case:
 
 
 def case_seed(name):
-    return 1000 + [c.name for c in CASES].index(name)
+    return 1000 + [c.name for c in CASES + MLP_CASES].index(name)
+
+
+def min_classes(case: Case):
+    """The class each state minimises: 1 everywhere for two classes (and for every case of
+    CASES), (2, 0, 1) from three classes on, so a wrong state's class shows."""
+    return (2, 0, 1) if case.net and case.net[-1] >= 3 else (1, 1, 1)
 
 
 # ------------------------------------------------------------------ the ops in numpy fp64
@@ -530,7 +568,7 @@ class Synth:
         srng = np.random.default_rng(case_seed(case.name) + 500)
         self.ml = (srng.uniform(0.05, 0.5, D), srng.uniform(-0.5, 0.5, D))
         self.scaler = Scaler(*self.ml)
-        self.W, self.bs = net((D, 32, 16, 2), case_seed(case.name) + 700)
+        self.W, self.bs = net((D,) + (case.net or (32, 16, 2)), case_seed(case.name) + 700)
         self.constraints_fn = lambda x: eval_ops(ops, x)
         fpath = os.path.join(str(tmp_path), f"features_{case.name}.csv")
         cpath = os.path.join(str(tmp_path), f"constraints_{case.name}.csv")
@@ -541,7 +579,7 @@ class Synth:
         with open(cpath, "w") as fh:
             fh.write("min,max\n" + "0.0,1.0\n" * case.C)
         self.constraints = SynthConstraints(fpath, cpath, ops, case.expr)
-        self.probs = [self.problem(X[s]) for s in range(B)]
+        self.probs = [self.problem(X[s], mc) for s, mc in zip(range(B), min_classes(case))]
 
     def expressions(self):
         """{column: expression} of the restated columns."""
@@ -553,9 +591,9 @@ class Synth:
         prog = self.constraints.device_program()
         return (len(prog.pool) + len(prog.expr_code)) & 1
 
-    def problem(self, x_init):
+    def problem(self, x_init, min_class=1):
         return mo.make_problem(self.lay, x_init, self.fmin, self.fmax, self.ml, self.W, self.bs,
-                               self.constraints_fn, 1, 2, True)
+                               self.constraints_fn, min_class, 2, True)
 
     def gene_of(self, feature):
         return int(np.where(self.plain_feat == feature)[0][0])
@@ -598,7 +636,7 @@ class Synth:
 
 def build(case, tmp_path) -> Synth:
     if isinstance(case, str):
-        case = CASES_BY_NAME[case]
+        case = CASES_BY_NAME[case] if case in CASES_BY_NAME else MLP_BY_NAME[case]
     return Synth(case, tmp_path)
 
 

@@ -292,37 +292,18 @@ def test_wide_mlp_config_matches_fp32_reference():
 
 
 # ------------------------------------------------------------------ bf16 perf mode
-def _bf16(a):
-    """fp32 -> bf16 -> fp32, round to nearest even (v_cvt_pk_bf16_f32 on finite values)."""
-    u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
-    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
-    return r.astype(np.uint32).view(np.float32)
-
-
-def _bf16_forward(x_ml, mut, W, bs):
-    """The engine's bf16 perf-mode classifier restated in numpy: layer 1 over the mutable
-    features with bf16 weights/activations and the immutable features folded into an fp32
-    per-row bias (k_setup_states), hidden layers bf16 x bf16 with fp32 accumulation, final
-    Dense + softmax in fp32 (test infrastructure, not an oracle of the reference)."""
-    x = np.asarray(x_ml, np.float64).astype(np.float32)
-    imm = np.setdiff1d(np.arange(x.shape[1]), mut)
-    bias1 = bs[0].astype(np.float32) + x[:, imm].astype(np.float64) @ W[0][imm].astype(np.float64)
-    h = _bf16(x[:, mut]).astype(np.float64) @ _bf16(W[0][mut]).astype(np.float64) + bias1
-    h = np.maximum(h.astype(np.float32), 0)
-    for w, b in zip(W[1:-1], bs[1:-1]):
-        h = _bf16(h).astype(np.float64) @ _bf16(w).astype(np.float64) + b
-        h = np.maximum(h.astype(np.float32), 0)
-    z = h.astype(np.float64) @ W[-1].astype(np.float64) + bs[-1]
-    z = z - z.max(axis=1, keepdims=True)
-    e = np.exp(z)
-    return e / e.sum(axis=1, keepdims=True)
+# the numpy restatement of the bf16 arithmetic lives in tests/bf16_ref.py (variant A is the
+# function that stood here); every bf16 instance at a measured tolerance:
+# tests/test_gpu_bf16_routes.py
+import bf16_ref  # noqa: E402
+from bf16_ref import bf16 as _bf16, bf16_forward as _bf16_forward  # noqa: E402,F401
 
 
 @pytest.mark.parametrize("wide", [False, True])
 def test_bf16_mode_classifier(wide):
     """mv_set_mlp_precision(bf16): k_mlp2 (shipped botnet net) / k_mlpw (configs[4] wide net;
-    with biases and at its other widths: tests/test_gpu_classifier_routes.py) on bf16 MFMA.  f1 matches the numpy restatement of the bf16 arithmetic (accumulation order
-    aside: 2e-3 absolute), stays close to the fp32 parity value (0.05 absolute on these rows),
+    with biases and at its other widths: tests/test_gpu_classifier_routes.py) on bf16 MFMA.  f1 matches the numpy restatement of the bf16 arithmetic at 4 x the floor
+    measured on the same rows (tests/bf16_ref.py; never above the earlier 2e-3), stays close to the fp32 parity value (0.05 absolute on these rows),
     f2/f3 are unchanged, and an attack in bf16 mode reports the bf16 f1 of its final genes."""
     from moeva2_amd.attacks.moeva2.classifier import Classifier, DenseMLPModel
     from moeva2_amd.io.tf_bundle import DenseMLP
@@ -367,8 +348,10 @@ def test_bf16_mode_classifier(wide):
         worst = 0.0
         for b in range(X.shape[0]):
             x_ml = mo.genetic_to_ml(p.lay, genes[b], X[b]) * p.ml[0] + p.ml[1]
-            emu = _bf16_forward(x_ml, mut, W, bs)[:, 1]
-            np.testing.assert_allclose(F16[b, :, 0], emu, rtol=0, atol=2e-3)
+            emu, floor = bf16_ref.f1_with_floor(x_ml, mut, W, bs, 1)
+            err = float(np.abs(F16[b, :, 0] - emu).max())
+            print(f"  bf16 evaluate, state {b}: floor {floor:.3e}, |device - A| {err:.3e}")
+            assert err <= min(2e-3, 4 * floor), (b, err, floor)
             worst = max(worst, float(np.abs(F16[b, :, 0] - F32[b, :, 0]).max()))
         print(f"bf16 vs fp32 f1: max |diff| {worst:.2e}")
         assert worst < 0.05
@@ -382,10 +365,13 @@ def test_bf16_mode_classifier(wide):
         torch.cuda.synchronize()
         g, Fa = g.cpu().numpy(), Fa.cpu().numpy()
         assert np.isfinite(Fa).all()
+        mut_a = mut[eng.stored_genes()]  # the fixed genes' features join the fp32 bias fold
         for b in range(X.shape[0]):
             x_ml = mo.genetic_to_ml(p.lay, g[b], X[b]) * p.ml[0] + p.ml[1]
-            np.testing.assert_allclose(Fa[b, :, 0], _bf16_forward(x_ml, mut, W, bs)[:, 1],
-                                       rtol=0, atol=2e-3)
+            emu, floor = bf16_ref.f1_with_floor(x_ml, mut_a, W, bs, 1)
+            err = float(np.abs(Fa[b, :, 0] - emu).max())
+            print(f"  bf16 attack, state {b}: floor {floor:.3e}, |device - A| {err:.3e}")
+            assert err <= min(2e-3, 4 * floor), (b, err, floor)
     finally:
         eng.set_mlp_precision("fp32")
 

@@ -14,10 +14,21 @@ Columns: mlp kind = mv_get_mlp_kernel (-1 none, 0 k_mlp, 1 / 2 k_mlp2 genes / ML
 
 What the table shows beyond the routes the GPU tests run:
   * k_mlp (kind 0) is product-reachable: fp32 nets whose k_mlpw32 tile passes the CU's 160 KiB
-    (512-wide with Dm4 >= 640), hidden widths that are no multiple of 16 or above 512, wide
-    nets of more than 8 classes; bf16 nets past k_mlpw's LDS.
+    (512-wide with Dm4 >= 624 or 640, by the final layer's size) and bf16 nets past k_mlpw's
+    LDS.  (The lines with hidden widths that are no multiple of 16 or above 512, or with more
+    than 8 classes, show mlp_route alone: mv_engine_create refuses those nets.)
   * Dm4 % 16 != 0 cannot occur (Dm4 is Dm rounded up to 16 where the problem is created).
   * 48 states of 100 offspring on 256 CUs run 960 workgroups of 5 rows (1,200 of 4 on 304).
+
+The "mlp synth" lines are the classifier-fallback cases of tests/synth_problem.py MLP_CASES
+(tests/test_gpu_mlp_fallback.py, tests/test_gpu_bf16_routes.py; tests/test_mlp_orders_cpu.py
+checks each line against its case): the k_mlp<MAXCT, BF> instance each case names, in the fp32
+and the bf16 mode and under MV_MLP_V1 (m639t: with MV_MLPR=0).  The MV_MLP_V1 and MV_MLPW lines
+are problems whose fp32 ML rows are written (xml_direct 0), as mv_engine_create makes them under
+those switches: the kernels they select read the rows, never the genes.  The "lds" lines give the three budgets at both sides
+of each edge the cases sit at: k_mlpw32 fits a 512-512-2 net at Dm4 608 and not at 624;
+mv_engine_create accepts that net up to Dm4 720, 512-272-3 up to 736 and 144-240-3 up to 1008;
+on botnet (Dm4 432) a 512-wide last hidden layer with 8 classes puts the bf16 mode past k_mlpw.
 
 The "row synth" lines are the synthetic shapes of tests/synth_problem.py, one per GPU case of
 tests/test_gpu_row_routes.py ("/sbx": the case's second run).  The name gives the attack's
@@ -71,15 +82,38 @@ mlp MV_MLPR_RW=2 botnet ... 3 classes  kind=6 rw=2 no=8 xml=0 cj=0 bf=0 direct=0
 mlp MV_MLPR_RW=2 lcld 64-32-2          kind=7 rw=1 no=2 xml=1 cj=0 bf=0 direct=0 co=0 maxct=0
 mlp MV_MLPR_RW=7 botnet 312-64-64-32-2 kind=6 rw=2 no=2 xml=0 cj=0 bf=0 direct=0 co=0 maxct=0
 mlp MV_MLP_V1 botnet hidden 128        kind=5 rw=0 no=0 xml=0 cj=1 bf=0 direct=0 co=0 maxct=0
-mlp MV_MLP_V1 botnet 312-64-64-32-2    kind=6 rw=1 no=2 xml=0 cj=0 bf=0 direct=0 co=0 maxct=0
+mlp MV_MLP_V1 botnet 312-64-64-32-2    kind=7 rw=1 no=2 xml=1 cj=0 bf=0 direct=0 co=0 maxct=0
 mlp MV_MLP_V1 bf16 hidden 128          kind=4 rw=0 no=0 xml=0 cj=1 bf=0 direct=0 co=0 maxct=0
 mlp MV_MLPW bf16 hidden 64             kind=4 rw=0 no=0 xml=0 cj=1 bf=0 direct=0 co=0 maxct=0
-mlp MV_MLPW fp32 hidden 128            kind=1 rw=0 no=0 xml=0 cj=2 bf=0 direct=1 co=1 maxct=0
+mlp MV_MLPW fp32 hidden 128            kind=2 rw=0 no=0 xml=0 cj=2 bf=0 direct=0 co=0 maxct=0
 mlp MV_MLPW_OFF bf16 hidden 256        kind=0 rw=0 no=0 xml=0 cj=0 bf=1 direct=0 co=0 maxct=4
 mlp MV_MLPW_OFF bf16 hidden 64         kind=1 rw=0 no=0 xml=0 cj=1 bf=1 direct=1 co=0 maxct=0
 mlp MV_MLPW32=0 fp32 hidden 144        kind=0 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=4
 mlp MV_MLPW32=0 fp32 hidden 512        kind=0 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=8
 mlp MV_MLP_CO=0 botnet hidden 80       kind=1 rw=0 no=0 xml=0 cj=2 bf=0 direct=1 co=0 maxct=0
+mlp synth m608w Dm4 608 512-512-2 fp32 kind=5 rw=0 no=0 xml=0 cj=4 bf=0 direct=0 co=0 maxct=0
+mlp synth m609w Dm4 624 512-512-2 fp32 kind=0 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=8
+mlp synth m609w Dm4 624 512-512-2 bf16 kind=0 rw=0 no=0 xml=0 cj=0 bf=1 direct=0 co=0 maxct=8
+mlp synth m736w Dm4 736 512-272-3 fp32 kind=0 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=8
+mlp synth m1008w Dm4 1008 144-240-3 fp32 kind=0 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=4
+mlp synth m1008w Dm4 1008 144-240-3 bf16 kind=0 rw=0 no=0 xml=0 cj=0 bf=1 direct=0 co=0 maxct=4
+mlp synth m640n Dm4 640 48-80-2 fp32   kind=1 rw=0 no=0 xml=0 cj=2 bf=0 direct=1 co=1 maxct=0
+mlp synth m640n Dm4 640 48-80-2 fp32 MV_MLP_V1 kind=0 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=2
+mlp synth m639t Dm4 640 32-16-8 fp32   kind=1 rw=0 no=0 xml=0 cj=1 bf=0 direct=1 co=0 maxct=0
+mlp synth m639t Dm4 640 32-16-8 fp32 MV_MLP_V1 kind=0 rw=0 no=0 xml=0 cj=0 bf=0 direct=0 co=0 maxct=1
+mlp MV_MLP_V1 even Dm 640-32-16-8      kind=7 rw=1 no=8 xml=1 cj=0 bf=0 direct=0 co=0 maxct=0
+mlp bf16 botnet 756-512-512-8          kind=0 rw=0 no=0 xml=0 cj=0 bf=1 direct=0 co=0 maxct=8
+mlp bf16 botnet 756-512-256-8          kind=4 rw=0 no=0 xml=0 cj=4 bf=0 direct=0 co=0 maxct=0
+lds Dm4 608-512-512-2 k_mlp=147856 create=ok k_mlpw32=161040 k_mlpw=166160
+lds Dm4 624-512-512-2 k_mlp=149904 create=ok k_mlpw32=165136 k_mlpw=174352
+lds Dm4 720-512-512-2 k_mlp=162192 create=ok k_mlpw32=189712 k_mlpw=198928
+lds Dm4 736-512-512-2 k_mlp=164240 create=refused k_mlpw32=193808 k_mlpw=198928
+lds Dm4 736-512-272-3 k_mlp=163408 create=ok k_mlpw32=192976 k_mlpw=200144
+lds Dm4 752-512-272-3 k_mlp=165456 create=refused k_mlpw32=197072 k_mlpw=208336
+lds Dm4 1008-144-240-3 k_mlp=163024 create=ok k_mlpw32=262224 k_mlpw=273488
+lds Dm4 1024-144-240-3 k_mlp=165072 create=refused k_mlpw32=266320 k_mlpw=273488
+lds Dm4 432-512-512-8 k_mlp=147872 create=ok k_mlpw32=148768 k_mlpw=166176
+lds Dm4 432-512-256-8 k_mlp=139680 create=ok k_mlpw32=140576 k_mlpw=157984
 row botnet full layout V 432           kind=2 nt=7 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0
 row botnet compact V 312 Vr 432        kind=2 nt=5 ident=1 sbx=0 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0
 row botnet SBX                         kind=2 nt=7 ident=1 sbx=1 slim=1 cons=0 nv=0 full=0 need_plan=1 plan_missing=0
