@@ -323,6 +323,43 @@ int mv_boost_create(int32_t device, const mv_boost_desc* boost, mv_forest** out)
  * (k_boost walking a per-workgroup LDS copy: the packed nodes fit 64 KiB). */
 int mv_engine_set_boost(mv_engine* e, const mv_boost_desc* boost);
 
+/* ---- Kernel machines and logistic regression (engine extension): scikit-learn's SVC / NuSVC
+ * (probability=True, two classes) and LogisticRegression predict_proba, restated in
+ * moeva2_amd/models/svm.py.  Per row, cast to fp32 first: s_v = the fma chain over the features
+ * in ascending order of x.v (linear, poly) or (x - v)^2 (rbf), from 0; K_v = s_v (linear),
+ * powi(gamma * s_v + coef0, degree) (poly, libsvm's square-and-multiply) or E(-(gamma * s_v))
+ * (rbf; E is mv_det_exp's function); dec[o] = sum over v ascending of coef[o][v] * K_v (multiply,
+ * then add, from 0), then + intercept[o]; without coef dec[o] = K_o + intercept[o].  Links:
+ * 0 = Platt's sigmoid of -dec[0] with probA / probB, clipped to [1e-7, 1 - 1e-7], then libsvm's
+ * pairwise coupling for two classes (eps 0.0025, at most 100 iterations); 1 = p1 =
+ * 1 / (1 + E(-dec[0])), p0 = 1 - p1; 2 = the softmax of mv_boost_desc.
+ * Refused with MV_ERR_ARG: n_vec < 1, n_features < 1, n_vec * n_features > 2^24, classes outside
+ * 2..8, a kernel or link outside the lists, links 0 / 1 without (2 classes, n_out 1), link 2
+ * without (3..8 classes, n_out == n_classes), no coef with n_vec != n_out, a degree outside
+ * 0..64, any entry or parameter that is not finite. */
+typedef struct mv_svm_desc {
+  int32_t n_features;       /* D: the width of a row */
+  int32_t n_classes;        /* 2..8 */
+  int32_t n_out;            /* decisions: 1 for two classes, else n_classes */
+  int32_t n_vec;            /* support vectors, or coefficient rows (no coef) */
+  int32_t kernel;           /* 0 linear, 1 poly, 2 rbf */
+  int32_t degree;           /* poly */
+  int32_t link;             /* 0 platt + coupling, 1 sigmoid, 2 softmax */
+  double gamma, coef0;      /* poly, rbf */
+  double probA, probB;      /* link 0 */
+  const double* vectors;    /* host [n_vec][n_features] */
+  const double* coef;       /* host [n_out][n_vec], or NULL: identity */
+  const double* intercept;  /* host [n_out] */
+} mv_svm_desc;
+/* Such a model behind the forest handle: mv_forest_predict, mv_forest_destroy and
+ * mv_objcalc_run_forest take it unchanged and run k_svm. */
+int mv_svm_create(int32_t device, const mv_svm_desc* svm, mv_forest** out);
+/* mv_engine_set_boost for such a model: the same preconditions and error codes (an engine
+ * created with model == NULL, no other classifier set, before mv_set_states: MV_ERR_STATE
+ * otherwise, no device call; svm->n_features must be the problem's D).  mv_get_mlp_kernel then
+ * reports 11 (k_svm). */
+int mv_engine_set_svm(mv_engine* e, const mv_svm_desc* svm);
+
 typedef struct mv_attack_params {
   int32_t n_gen;          /* Moeva2 n_gen (termination "n_gen") */
   int32_t pop_size;       /* P = n_ref_points + n_obj (203 for n_pop 200) */
@@ -444,7 +481,8 @@ int mv_get_row_kernel(mv_engine* e, int32_t* kind);
  * 2 = k_mlp2 reading the fp32 ML rows, 4 = k_mlpw (bf16 weights), 5 = k_mlpw32 (fp32 wide
  * nets: 64-row tiles, one activation buffer), 6 / 7 = k_mlpr reading the genes / the fp32 ML
  * rows, 8 = k_forest (a tree ensemble, mv_engine_set_forest), 9 / 10 = k_boost (a boosted
- * ensemble, mv_engine_set_boost) over global memory / LDS, -1 = no device classifier
+ * ensemble, mv_engine_set_boost) over global memory / LDS, 11 = k_svm (a kernel machine or
+ * logistic regression, mv_engine_set_svm), -1 = no device classifier
  * (3, the retired k_mlp2x, is no longer returned).
  * Lets a profiler price the ML-row bytes of the row kernel and the classifier. */
 int mv_get_mlp_kernel(mv_engine* e, int32_t* kind);
@@ -471,6 +509,12 @@ int mv_det_pow(int64_t n, const double* x, const double* y, double* out);
  * det_exp2(x, 0.0): fdlibm's exp, the same IEEE operation sequence as k_boost's):
  * out[i] = E(x[i]) for host arrays.  models/boost.py's specification calls it. */
 int mv_det_exp(int64_t n, const double* x, double* out);
+/* The feature sums of k_svm (host build of csrc/svm.h svm_term, one fma per feature in
+ * ascending order from 0): out[i][v] = sum_j x[i][j] * vectors[v][j], or of
+ * (x[i][j] - vectors[v][j])^2 when rbf != 0, for host arrays x [n][D], vectors [n_vec][D].
+ * models/svm.py's specification calls it. */
+int mv_svm_sums(int64_t n, int32_t D, int32_t n_vec, int32_t rbf, const double* x,
+                const double* vectors, double* out);
 
 /* ---- C-PGD: the constrained gradient attack (src/attacks/pgd/atk.py:74-163 on ART's PGD
  * loop, src/attacks/pgd/classifier.py:107-332 loss_gradient), whole loop on device.  All

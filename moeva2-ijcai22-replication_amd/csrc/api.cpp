@@ -174,8 +174,8 @@ struct mv_engine {
   int* off_scr = nullptr;
   bool attack_ready = false;
   bool has_model = false;
-  // mv_engine_set_forest / mv_engine_set_boost: a tree ensemble is the classifier (p.forest:
-  // k_forest, or p.boost: k_boost)
+  // mv_engine_set_forest / mv_engine_set_boost / mv_engine_set_svm: a table model is the
+  // classifier (p.forest: k_forest, p.boost: k_boost, or p.svm: k_svm)
   bool has_forest = false;
   long long* d_phase = nullptr;  // MV_SURV_PHASES=1: survival phase clocks [B][16]
   long long* d_gphase = nullptr; // MV_GEN_PHASES=1: k_genc clocks [grid][8] (one group)
@@ -830,8 +830,9 @@ int mv_set_states(mv_engine* e, int32_t B, const double* x_init, const double* x
   HIPCHK(hipSetDevice(e->device));
   // a model-less engine (host classifier plugin) evaluates f2 / f3 only: no class check
   const int nout = e->has_model    ? e->p.dims[e->p.n_layers]
-                   : e->has_forest ? (e->p.boost.n_trees > 0 ? e->p.boost.n_classes
-                                                             : e->p.forest.n_classes)
+                   : e->has_forest ? (e->p.svm.n_vec > 0       ? e->p.svm.n_classes
+                                      : e->p.boost.n_trees > 0 ? e->p.boost.n_classes
+                                                               : e->p.forest.n_classes)
                                    : INT32_MAX;
   for (int b = 0; b < B; ++b)
     if (minimize_class[b] < 0 || minimize_class[b] >= nout)
@@ -2024,6 +2025,7 @@ struct mv_forest {
   int D = 0;
   DForest f{};
   DBoost b{};  // mv_boost_create: b.n_trees > 0 and f is empty; the handle runs k_boost
+  DSvm s{};    // mv_svm_create: s.n_vec > 0 and f, b are empty; the handle runs k_svm
   std::vector<void*> allocs;
   ~mv_forest() {
     (void)hipSetDevice(device);
@@ -2119,9 +2121,91 @@ static hipError_t boost_upload(const mv_boost_desc* d, const std::vector<BoostNo
   return err;
 }
 
-// mv_forest_predict / mv_objcalc_run_forest on either kind of handle
+// ---- kernel machines and logistic regression (svm.hip)
+
+// Everything models/svm.py's SvmTables.validate refuses, before any device call.
+static int svm_check(const mv_svm_desc* d) {
+  if (!d || !d->vectors || !d->intercept) return fail(MV_ERR_ARG, "svm: null table");
+  if (d->n_features < 1) return fail(MV_ERR_ARG, "svm: n_features < 1");
+  if (d->n_vec < 1) return fail(MV_ERR_ARG, "svm: n_vec < 1");
+  if ((long long)d->n_vec * d->n_features > SVM_MAX_ENTRIES)
+    return fail(MV_ERR_ARG, "svm: n_vec * n_features above 2^24");
+  if (d->n_classes < 2 || d->n_classes > SVM_MAX_CLASSES)
+    return fail(MV_ERR_ARG, "svm: 2..8 classes");
+  if (d->kernel != SVM_LINEAR && d->kernel != SVM_POLY && d->kernel != SVM_RBF)
+    return fail(MV_ERR_ARG, "svm: kernel must be linear (0), poly (1) or rbf (2)");
+  if (d->link != SVM_LINK_PLATT && d->link != SVM_LINK_SIGMOID && d->link != SVM_LINK_SOFTMAX)
+    return fail(MV_ERR_ARG, "svm: link must be platt (0), sigmoid (1) or softmax (2)");
+  if (d->link == SVM_LINK_SOFTMAX ? (d->n_classes < 3 || d->n_out != d->n_classes)
+                                  : (d->n_classes != 2 || d->n_out != 1))
+    return fail(MV_ERR_ARG, "svm: platt and sigmoid take two classes and one decision, softmax "
+                            "3..8 classes and one decision each");
+  if (!d->coef && d->n_vec != d->n_out)
+    return fail(MV_ERR_ARG, "svm: without coef the vectors are the decisions' (n_vec == n_out)");
+  if (d->degree < 0 || d->degree > SVM_MAX_DEGREE) return fail(MV_ERR_ARG, "svm: degree 0..64");
+  for (const double v : {d->gamma, d->coef0, d->probA, d->probB})
+    if (!std::isfinite(v)) return fail(MV_ERR_ARG, "svm: a parameter is not finite");
+  const size_t nvd = (size_t)d->n_vec * d->n_features;
+  for (size_t i = 0; i < nvd; ++i)
+    if (!std::isfinite(d->vectors[i])) return fail(MV_ERR_ARG, "svm: a vector entry is not finite");
+  if (d->coef)
+    for (size_t i = 0; i < (size_t)d->n_out * d->n_vec; ++i)
+      if (!std::isfinite(d->coef[i])) return fail(MV_ERR_ARG, "svm: a coefficient is not finite");
+  for (int o = 0; o < d->n_out; ++o)
+    if (!std::isfinite(d->intercept[o])) return fail(MV_ERR_ARG, "svm: an intercept is not finite");
+  return MV_OK;
+}
+
+// svm.h DSvm::vp's layout; slot (engine rows) may be null (mv_svm_create)
+static hipError_t svm_upload(const mv_svm_desc* d, const int* slot_of, DSvm& s,
+                             std::vector<void*>& allocs) {
+  const int D = d->n_features, Dp = (D + SVM_FC - 1) / SVM_FC * SVM_FC;
+  const int nb = (d->n_vec + SVM_VB - 1) / SVM_VB;
+  std::vector<double> vp((size_t)nb * Dp * SVM_VB, 0.0);
+  for (int v = 0; v < d->n_vec; ++v)
+    for (int j = 0; j < D; ++j)
+      vp[((size_t)(v / SVM_VB) * Dp + j) * SVM_VB + v % SVM_VB] = d->vectors[(size_t)v * D + j];
+  hipError_t err = hipSuccess;
+  auto K = [&](auto** dst, const auto* host, size_t n) {
+    if (err != hipSuccess) return;
+    err = upload(dst, host, n);
+    if (err == hipSuccess) allocs.push_back((void*)*dst);
+  };
+  s = DSvm{};
+  K((double**)&s.vp, vp.data(), vp.size());
+  if (d->coef) K((double**)&s.coef, d->coef, (size_t)d->n_out * d->n_vec);
+  K((double**)&s.intercept, d->intercept, (size_t)d->n_out);
+  if (slot_of) {
+    std::vector<int> slot((size_t)Dp, 0);
+    for (int j = 0; j < D; ++j) slot[j] = slot_of[j];
+    K((int**)&s.slot, slot.data(), slot.size());
+  }
+  s.n_vec = d->n_vec;
+  s.n_out = d->n_out;
+  s.n_classes = d->n_classes;
+  s.D = D;
+  s.Dp = Dp;
+  s.kernel = d->kernel;
+  s.degree = d->degree;
+  s.link = d->link;
+  s.gamma = d->gamma;
+  s.coef0 = d->coef0;
+  s.probA = d->probA;
+  s.probB = d->probB;
+  return err;
+}
+
+// mv_forest_predict / mv_objcalc_run_forest on any kind of handle
 static hipError_t forest_handle_predict(const mv_forest* f, int rows, const double* x,
                                         double* proba, hipStream_t st) {
+  if (f->s.n_vec > 0) {
+    SvmArgs sa{};
+    sa.f = f->s;
+    sa.total = rows;
+    sa.x = x;
+    sa.proba = proba;
+    return launch_svm_predict(sa, st);
+  }
   if (f->b.n_trees > 0) {
     BoostArgs ba{};
     ba.f = f->b;
@@ -2165,7 +2249,9 @@ int mv_objcalc_run_forest(mv_objcalc* o, mv_engine* e, mv_forest* f, int32_t B, 
   auto predict = [&](int rows, const double* xm, double* proba, hipStream_t st) {
     return forest_handle_predict(f, rows, xm, proba, st);
   };
-  const int n_out = f->b.n_trees > 0 ? f->b.n_classes : f->f.n_classes;
+  const int n_out = f->s.n_vec > 0     ? f->s.n_classes
+                    : f->b.n_trees > 0 ? f->b.n_classes
+                                       : f->f.n_classes;
   return objcalc_run(o, e, f->D, n_out, f->device, predict, B, n, x_init, x, minimize_class, obj,
                      range_bad, stream_);
 }
@@ -2282,6 +2368,64 @@ int mv_engine_set_boost(mv_engine* e, const mv_boost_desc* d) {
   return MV_OK;
 }
 
+int mv_svm_create(int32_t device, const mv_svm_desc* d, mv_forest** out) {
+  if (!out) return fail(MV_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (const int rc = svm_check(d)) return rc;
+  HIPCHK(hipSetDevice(device));
+  mv_forest* f = new mv_forest();
+  f->device = device;
+  f->D = d->n_features;
+  const hipError_t err = svm_upload(d, nullptr, f->s, f->allocs);
+  if (err != hipSuccess) {
+    delete f;
+    return fail(MV_ERR_HIP, std::string("upload: ") + hipGetErrorString(err));
+  }
+  *out = f;
+  return MV_OK;
+}
+
+int mv_engine_set_svm(mv_engine* e, const mv_svm_desc* d) {
+  if (!e || !d) return fail(MV_ERR_ARG, "null argument");
+  // every refusal comes before the first device call (mv_engine_set_boost's, in its order)
+  if (e->has_model)
+    return fail(MV_ERR_STATE, "mv_engine_set_svm: the engine was created with an MLP");
+  if (e->has_forest)
+    return fail(MV_ERR_STATE, "mv_engine_set_svm: a classifier is already set");
+  if (e->B > 0) return fail(MV_ERR_STATE, "mv_engine_set_svm must come before mv_set_states");
+  if (const int rc = svm_check(d)) return rc;
+  if (d->n_features != e->p.D) return fail(MV_ERR_ARG, "svm: n_features != D");
+  // a feature's value: mv_engine_set_forest's slots
+  std::vector<int> slot(e->p.D);
+  for (int f = 0; f < e->p.D; ++f) slot[f] = e->p.Dm4 + f;
+  for (int j = 0; j < e->hp.Dm; ++j) slot[e->hp.mut[j]] = j;
+  HIPCHK(hipSetDevice(e->device));
+  const hipError_t err = svm_upload(d, slot.data(), e->p.svm, e->prob_allocs);
+  if (err != hipSuccess) {
+    e->p.svm = DSvm{};
+    return fail(MV_ERR_HIP, std::string("upload: ") + hipGetErrorString(err));
+  }
+  e->has_forest = true;
+  return MV_OK;
+}
+
+int mv_svm_sums(int64_t n, int32_t D, int32_t n_vec, int32_t rbf, const double* x,
+                const double* vectors, double* out) {
+  if (n < 0 || D < 1 || n_vec < 1 || !vectors || (n > 0 && (!x || !out)))
+    return fail(MV_ERR_ARG, "bad mv_svm_sums arguments");
+  for (int64_t i = 0; i < n; ++i)
+    for (int v = 0; v < n_vec; ++v) {
+      const double *xi = x + (size_t)i * D, *vv = vectors + (size_t)v * D;
+      double s = 0.0;
+      if (rbf)
+        for (int j = 0; j < D; ++j) s = svm_term<true>(s, xi[j], vv[j]);
+      else
+        for (int j = 0; j < D; ++j) s = svm_term<false>(s, xi[j], vv[j]);
+      out[(size_t)i * n_vec + v] = s;
+    }
+  return MV_OK;
+}
+
 int mv_objcalc_score(mv_objcalc* o, int32_t B, int32_t n, const double* x_init, const double* x,
                      const double* G, int32_t C, const double* proba, int32_t n_out,
                      int32_t minimize_class, double* obj, int32_t* range_bad, void* stream_) {
@@ -2324,15 +2468,16 @@ int mv_debug_checks(int32_t* record, int32_t* compiled) {
   if (!record) return fail(MV_ERR_ARG, "null record");
   if (compiled) *compiled = MV_CHECKS_ON;
   HIPCHK(hipDeviceSynchronize());
-  int ev[8], sv[8], pg[8], fo[8], bo[8];
+  int ev[8], sv[8], pg[8], fo[8], bo[8], sm[8];
   HIPCHK(take_checks_eval(ev));
   HIPCHK(take_checks_survive(sv));
   HIPCHK(take_checks_pgd(pg));
   HIPCHK(take_checks_forest(fo));
   HIPCHK(take_checks_boost(bo));
-  const int* r = ev[0] ? ev : (sv[0] ? sv : (pg[0] ? pg : (fo[0] ? fo : bo)));
+  HIPCHK(take_checks_svm(sm));
+  const int* r = ev[0] ? ev : (sv[0] ? sv : (pg[0] ? pg : (fo[0] ? fo : (bo[0] ? bo : sm))));
   for (int k = 0; k < 8; ++k) record[k] = r[k];
-  record[5] = ev[5] + sv[5] + pg[5] + fo[5] + bo[5];
+  record[5] = ev[5] + sv[5] + pg[5] + fo[5] + bo[5] + sm[5];
   return MV_OK;
 }
 

@@ -54,6 +54,7 @@ enum : int {
   CK_BOOST_NODE = 31,   // k_boost: node index outside [0, n_nodes)
   CK_BOOST_SLOT = 32,   // k_boost: value slot outside the ML row / the state's fixed vector
   CK_BOOST_OUT = 33,    // k_boost: a tree's raw-score index outside [0, n_outputs)
+  CK_SVM_SLOT = 34,     // k_svm: value slot outside the ML row / the state's fixed vector
 };
 // survival dump (checks builds): [0] 1 = valid, [1] gen, [2] state in its group, [3] N,
 // [4, 7) carried ideal, [7, 10) carried worst, [10, 19) carried extremes, [19] has_extreme,
@@ -117,6 +118,7 @@ hipError_t take_checks_survive(int* out);
 hipError_t take_checks_pgd(int* out);
 hipError_t take_checks_forest(int* out);
 hipError_t take_checks_boost(int* out);
+hipError_t take_checks_svm(int* out);
 hipError_t take_survival_dump(double* out);  // [SURV_DUMP_N], cleared
 
 }  // namespace mv

@@ -15,6 +15,7 @@
 
 #include "boost.h"
 #include "forest.h"
+#include "svm.h"
 
 // MV_CLOCKS (development builds: `make variant NAME=clk DEFS=-DMV_CLOCKS=1`): the k_genc /
 // k_mlp2 / k_survive phase clocks behind MV_GEN_PHASES / MV_MLP_PHASES / MV_SURV_PHASES.
@@ -146,6 +147,9 @@ struct DProblem {
   // ... or a gradient-boosted ensemble (mv_engine_set_boost; boost.h): boost.n_trees > 0, the
   // same rows and xfix, k_boost reads them
   DBoost boost;
+  // ... or a kernel machine / logistic regression (mv_engine_set_svm; svm.h): svm.n_vec > 0,
+  // the same rows and xfix, k_svm reads them
+  DSvm svm;
 };
 
 struct DStates {

@@ -2724,6 +2724,24 @@ hipError_t launch_mlp(const RowsArgs& a, int slot, int hist_row0, hipStream_t st
       ba.hist_row0 = hist_row0;
       return launch_boost_rows(ba, r.kind == BOOST_ROWS_LDS, stream);
     }
+    case SVM_ROWS: {  // svm.hip k_svm over the same rows
+      SvmArgs sa{};
+      sa.f = p.svm;
+      sa.total = a.total;
+      sa.n = a.n;
+      sa.Dm4 = p.Dm4;
+      sa.xml = a.xml;
+      sa.xfix = a.s.xfix;
+      sa.min_class = a.s.min_class;
+      sa.out_map = a.out_map;
+      sa.F = a.F;
+      sa.out_rows = a.out_rows;
+      sa.hist = a.hist;
+      sa.hist_rows = a.hist_rows;
+      sa.hist_w = a.hist_w;
+      sa.hist_row0 = hist_row0;
+      return launch_svm_rows(sa, stream);
+    }
     case MLPR_GENES:
     case MLPR_ROWS: {
       const size_t lds = mlpr_lds(p, r.rw).total;

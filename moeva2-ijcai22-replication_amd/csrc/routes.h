@@ -284,6 +284,7 @@ enum MlpKind {
   FOREST_ROWS = 8,  // k_forest (a tree ensemble) reading the fp32 ML rows and xfix
   BOOST_ROWS = 9,   // k_boost (a boosted ensemble), the nodes read from global memory (L2)
   BOOST_ROWS_LDS = 10,  // k_boost walking a per-workgroup LDS copy of the nodes (boost_lds_ok)
+  SVM_ROWS = 11,    // k_svm (a kernel machine or logistic regression) over the same rows
 };
 struct MlpRoute {
   int kind;     // MlpKind
@@ -304,6 +305,10 @@ inline MlpRoute mlp_route(const DProblem& p, const Switches& sw) {
   }
   if (p.boost.n_trees > 0) {  // mv_engine_set_boost: no MLP and no forest then
     r.kind = !sw.boost_lds_off && boost_lds_ok(p.boost) ? BOOST_ROWS_LDS : BOOST_ROWS;
+    return r;
+  }
+  if (p.svm.n_vec > 0) {  // mv_engine_set_svm: no MLP and no tree ensemble then
+    r.kind = SVM_ROWS;
     return r;
   }
   if (p.n_layers == 0) {

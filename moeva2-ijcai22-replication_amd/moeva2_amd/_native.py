@@ -44,6 +44,7 @@ EXPORTED = [
     "mv_forest_create", "mv_forest_destroy", "mv_forest_predict", "mv_engine_set_forest",
     "mv_objcalc_run_forest", "mv_front", "mv_survive_wide",
     "mv_boost_create", "mv_engine_set_boost", "mv_det_exp",
+    "mv_svm_create", "mv_engine_set_svm", "mv_svm_sums",
 ]
 
 _i32p = C.POINTER(C.c_int32)
@@ -93,6 +94,14 @@ class BoostDesc(C.Structure):
                 ("n_trees", C.c_int32), ("n_leaves", C.c_int32), ("n_nodes", C.c_int64),
                 ("feature", _i32p), ("threshold", _f64p), ("left", _i32p), ("right", _i32p),
                 ("tree_root", _i32p), ("leaf_value", _f64p), ("base", _f64p)]
+
+
+class SvmDesc(C.Structure):
+    _fields_ = [("n_features", C.c_int32), ("n_classes", C.c_int32), ("n_out", C.c_int32),
+                ("n_vec", C.c_int32), ("kernel", C.c_int32), ("degree", C.c_int32),
+                ("link", C.c_int32), ("gamma", C.c_double), ("coef0", C.c_double),
+                ("probA", C.c_double), ("probB", C.c_double), ("vectors", _f64p),
+                ("coef", _f64p), ("intercept", _f64p)]
 
 
 class PgdDesc(C.Structure):
@@ -202,6 +211,9 @@ def lib():
             "mv_boost_create": [C.c_int32, C.POINTER(BoostDesc), C.POINTER(vp)],
             "mv_engine_set_boost": [vp, C.POINTER(BoostDesc)],
             "mv_det_exp": [C.c_int64, _f64p, _f64p],
+            "mv_svm_create": [C.c_int32, C.POINTER(SvmDesc), C.POINTER(vp)],
+            "mv_engine_set_svm": [vp, C.POINTER(SvmDesc)],
+            "mv_svm_sums": [C.c_int64, C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, _f64p],
         }
         for name, args in sig.items():
             try:
@@ -269,6 +281,20 @@ def det_exp(x) -> np.ndarray:
     out = np.empty(x.shape, np.float64)
     f64 = lambda a: a.ctypes.data_as(_f64p)  # noqa: E731
     check(lib().mv_det_exp(x.size, f64(x), f64(out)))
+    return out
+
+
+def svm_sums(x, vectors, rbf) -> np.ndarray:
+    """The feature sums of k_svm (csrc/svm.h svm_term, one fma per feature in ascending order),
+    host build: x [n][D], vectors [n_vec][D] -> [n][n_vec] of x.v, or of |x - v|^2 when rbf."""
+    x = np.ascontiguousarray(np.atleast_2d(x), np.float64)
+    v = np.ascontiguousarray(np.atleast_2d(vectors), np.float64)
+    if x.shape[1] != v.shape[1]:
+        raise ValueError(f"x has {x.shape[1]} features, the vectors {v.shape[1]}")
+    out = np.empty((x.shape[0], v.shape[0]), np.float64)
+    f64 = lambda a: a.ctypes.data_as(_f64p)  # noqa: E731
+    check(lib().mv_svm_sums(x.shape[0], x.shape[1], v.shape[0], int(bool(rbf)), f64(x), f64(v),
+                            f64(out)))
     return out
 
 
@@ -413,6 +439,14 @@ class Engine:
         (mv_engine_set_boost): set_forest's preconditions and errors."""
         d, keep = _boost_desc(tables)
         _check_forest(lib().mv_engine_set_boost(self._h, C.byref(d)))
+        self.forest = tables
+        self.n_out = tables.n_classes
+
+    def set_svm(self, tables):
+        """Make a kernel machine or logistic regression (models.svm.SvmTables) the engine's
+        classifier (mv_engine_set_svm): set_forest's preconditions and errors."""
+        d, keep = _svm_desc(tables)
+        _check_forest(lib().mv_engine_set_svm(self._h, C.byref(d)))
         self.forest = tables
         self.n_out = tables.n_classes
 
@@ -575,10 +609,12 @@ class Engine:
                 "row_kernel": ("k_gen+k_cons", "k_narrow", "k_genc")[rk.value],
                 "mlp_kernel": {-1: None, 0: "k_mlp", 1: "k_mlp2(genes)", 2: "k_mlp2",
                                4: "k_mlpw", 5: "k_mlpw32", 6: "k_mlpr(genes)", 7: "k_mlpr",
-                               8: "k_forest", 9: "k_boost", 10: "k_boost(lds)"}[mk.value]}
+                               8: "k_forest", 9: "k_boost", 10: "k_boost(lds)",
+                               11: "k_svm"}[mk.value]}
 
     def mlp_kernel(self) -> int:
-        """mv_get_mlp_kernel's kind (csrc/routes.h MlpKind; 8 = k_forest, 9 / 10 = k_boost)."""
+        """mv_get_mlp_kernel's kind (csrc/routes.h MlpKind; 8 = k_forest, 9 / 10 = k_boost,
+        11 = k_svm)."""
         mk = C.c_int32()
         check(lib().mv_get_mlp_kernel(self._h, C.byref(mk)))
         return int(mk.value)
@@ -743,6 +779,51 @@ class Boost(Forest):
         d, keep = _boost_desc(tables)
         self._h = C.c_void_p()
         _check_forest(lib().mv_boost_create(device, C.byref(d), C.byref(self._h)))
+        self.n_out = int(tables.n_classes)
+        self.device = device
+
+
+def _svm_desc(t):
+    """SvmDesc of a models.svm.SvmTables (and the arrays it points into)."""
+    from .models.svm import KERNELS, LINKS
+
+    vec = np.ascontiguousarray(t.vectors, np.float64)
+    if vec.ndim != 2:
+        raise ValueError("vectors must be [n_vec][n_features]")
+    icpt = np.ascontiguousarray(t.intercept, np.float64).reshape(-1)
+    coef = None if t.coef is None else np.ascontiguousarray(t.coef, np.float64)
+    if coef is not None and coef.shape != (icpt.shape[0], vec.shape[0]):
+        raise ValueError(f"coef {coef.shape}: expected ({icpt.shape[0]}, {vec.shape[0]})")
+    if t.kernel not in KERNELS or t.link not in LINKS:
+        raise ValueError(f"kernel {t.kernel!r} / link {t.link!r} outside the engine's")
+    if float(t.degree) != int(t.degree):
+        raise ValueError(f"degree={t.degree!r} is not an integer")
+    if vec.shape[0] and vec.shape[1] != int(t.n_features):
+        raise ValueError("vectors' width is not n_features")
+    d = SvmDesc()
+    d.n_features = int(t.n_features)
+    d.n_classes = int(t.n_classes)
+    d.n_out = int(icpt.shape[0])
+    d.n_vec = int(vec.shape[0])
+    d.kernel = KERNELS.index(t.kernel)
+    d.degree = int(t.degree)
+    d.link = LINKS.index(t.link)
+    d.gamma, d.coef0 = float(t.gamma), float(t.coef0)
+    d.probA, d.probB = float(t.probA), float(t.probB)
+    d.vectors = vec.ctypes.data_as(_f64p)
+    d.coef = None if coef is None else coef.ctypes.data_as(_f64p)
+    d.intercept = icpt.ctypes.data_as(_f64p)
+    return d, [vec, coef, icpt]
+
+
+class Svm(Forest):
+    """Device kernel machine / logistic regression behind the forest handle (mv_svm_create):
+    predict, the destructor and ObjCalc.run are Forest's."""
+
+    def __init__(self, tables, device=0):
+        d, keep = _svm_desc(tables)
+        self._h = C.c_void_p()
+        _check_forest(lib().mv_svm_create(device, C.byref(d), C.byref(self._h)))
         self.n_out = int(tables.n_classes)
         self.device = device
 
@@ -1007,6 +1088,20 @@ def boost_predict_proba(tables, x):
     m = _FORESTS.get(id(tables))
     if m is None:
         m = _FORESTS[id(tables)] = (Boost(tables), tables)
+    m = m[0]
+    xd = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(x), np.float64)).cuda(m.device)
+    out = torch.empty((xd.shape[0], m.n_out), dtype=torch.float64, device=xd.device)
+    m.predict(xd, out)
+    return out.cpu().numpy()
+
+
+def svm_predict_proba(tables, x):
+    """forest_predict_proba for a models.svm.SvmTables."""
+    import torch
+
+    m = _FORESTS.get(id(tables))
+    if m is None:
+        m = _FORESTS[id(tables)] = (Svm(tables), tables)
     m = m[0]
     xd = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(x), np.float64)).cuda(m.device)
     out = torch.empty((xd.shape[0], m.n_out), dtype=torch.float64, device=xd.device)

@@ -11,6 +11,8 @@ RandomForestClassifier / ExtraTreesClassifier / DecisionTreeClassifier, or the `
 ``models.forest.ForestTables``, loads as a ``ForestModel`` whose trees run on the device.
 A ``.joblib`` holding a GradientBoostingClassifier (log-loss) / HistGradientBoostingClassifier,
 or the ``.npz`` of a ``models.boost.BoostTables``, loads as a ``BoostModel`` in the same way.
+A ``.joblib`` holding an SVC / NuSVC (``probability=True``, two classes) or a
+LogisticRegression, or the ``.npz`` of a ``models.svm.SvmTables``, loads as an ``SvmModel``.
 """
 import os
 
@@ -19,6 +21,7 @@ import numpy as np
 from ...io.tf_bundle import DenseMLP, load_dense_mlp
 from ...models.boost import BoostModel, BoostTables, is_sklearn_boost
 from ...models.forest import ForestModel, ForestTables, is_sklearn_trees
+from ...models.svm import SvmModel, SvmTables, is_sklearn_svm
 
 
 class DenseMLPModel:
@@ -60,9 +63,12 @@ def load_model(path: str):
         model = joblib.load(path)
         if is_sklearn_boost(model):
             return BoostModel(BoostTables.from_sklearn(model))
+        if is_sklearn_svm(model):
+            return SvmModel(SvmTables.from_sklearn(model))
         if not is_sklearn_trees(model):
             raise ValueError(f"{path} holds a {type(model).__name__}; expected a fitted "
-                             "scikit-learn forest, tree or gradient-boosting classifier")
+                             "scikit-learn forest, tree, gradient-boosting, SVC or "
+                             "LogisticRegression classifier")
         return ForestModel(ForestTables.from_sklearn(model))
     if path.endswith(".npz") or os.path.exists(path + ".npz"):
         d = np.load(path if path.endswith(".npz") else path + ".npz", allow_pickle=False)
@@ -70,6 +76,8 @@ def load_model(path: str):
             return ForestModel(ForestTables.load(path if path.endswith(".npz") else path + ".npz"))
         if "boost_tables" in d.files:
             return BoostModel(BoostTables.load(path if path.endswith(".npz") else path + ".npz"))
+        if "svm_tables" in d.files:
+            return SvmModel(SvmTables.load(path if path.endswith(".npz") else path + ".npz"))
         n = sum(1 for k in d.files if k.startswith("W"))
         return DenseMLPModel(DenseMLP([d[f"W{i}"] for i in range(n)],
                                       [d[f"b{i}"] for i in range(n)],
@@ -129,3 +137,18 @@ class Classifier:
             return self._boost
         raise NotImplementedError(
             f"{type(clf).__name__} is not a boosted ensemble the MI355X engine runs")
+
+    def svm_tables(self) -> SvmTables:
+        """Tables for the device run of a kernel machine or logistic regression (engine
+        extension): the model is a fitted scikit-learn SVC / NuSVC / LogisticRegression within
+        the engine's limits, an SvmTables or an SvmModel."""
+        clf = self._classifier
+        if callable(getattr(clf, "svm_tables", None)):
+            return clf.svm_tables()
+        if is_sklearn_svm(clf):
+            if getattr(self, "_svm", None) is None:
+                self._svm = SvmTables.from_sklearn(clf)
+            return self._svm
+        raise NotImplementedError(
+            f"{type(clf).__name__} is not a kernel machine or logistic regression the MI355X "
+            "engine runs")

@@ -58,9 +58,9 @@ class ObjectiveCalculator:
         device = int(device)
         objs = self._devs.get(device)
         if objs is None:
-            from ..._native import Boost, Forest, Mlp, ObjCalc
+            from ..._native import Boost, Forest, Mlp, ObjCalc, Svm
             from ...problem import (has_device_boost, has_device_classifier, has_device_forest,
-                                    has_device_program)
+                                    has_device_program, has_device_svm)
 
             masks = get_ohe_masks(self._constraints.get_feature_type())
             D = int(self._constraints.get_feature_type().shape[0])
@@ -80,6 +80,8 @@ class ObjectiveCalculator:
                 mlp = Forest(self._classifier.forest_tables(), device=device)
             elif has_device_boost(self._classifier):
                 mlp = Boost(self._classifier.boost_tables(), device=device)
+            elif has_device_svm(self._classifier):
+                mlp = Svm(self._classifier.svm_tables(), device=device)
             elif has_device_classifier(self._classifier):
                 w = self._classifier.dense_weights()
                 mlp = Mlp(w.weights, w.biases, device=device)

@@ -23,13 +23,26 @@ def has_device_program(constraints) -> bool:
 
 def has_device_classifier(classifier) -> bool:
     """True for Dense(relu)...Dense(softmax) models the engine runs on MFMA and for tree
-    ensembles it walks on the device (has_device_forest, has_device_boost); any other
+    ensembles it walks on the device (has_device_forest, has_device_boost) and kernel machines
+    (has_device_svm); any other
     ``predict_proba`` model is called on the host."""
     try:
         classifier.dense_weights()
         return True
     except (NotImplementedError, AttributeError, ValueError):
-        return has_device_forest(classifier) or has_device_boost(classifier)
+        return (has_device_forest(classifier) or has_device_boost(classifier)
+                or has_device_svm(classifier))
+
+
+def has_device_svm(classifier) -> bool:
+    """True when the classifier offers svm tables within the engine's limits (a fitted
+    scikit-learn SVC / NuSVC with probability=True and two classes, a LogisticRegression, an
+    SvmTables, an SvmModel)."""
+    try:
+        classifier.svm_tables()
+        return True
+    except (NotImplementedError, AttributeError, ValueError):
+        return False
 
 
 def has_device_boost(classifier) -> bool:
@@ -104,7 +117,10 @@ def get_engine(constraints, classifier, ml_scaler, norm, scale_objectives=True, 
         forest = classifier.forest_tables() if has_device_forest(classifier) else None
         boost = classifier.boost_tables() if forest is None and has_device_boost(classifier) \
             else None
-        mlp = classifier.dense_weights() if dev_clf and forest is None and boost is None else None
+        svm = classifier.svm_tables() if forest is None and boost is None \
+            and has_device_svm(classifier) else None
+        mlp = classifier.dense_weights() \
+            if dev_clf and forest is None and boost is None and svm is None else None
         s, m = scaler_arrays(ml_scaler) if dev_clf else (None, None)
         eng = Engine(build_device_program(constraints, has_device_program(constraints)),
                      mlp.weights if mlp else None, mlp.biases if mlp else None, s, m, norm,
@@ -113,6 +129,8 @@ def get_engine(constraints, classifier, ml_scaler, norm, scale_objectives=True, 
             eng.set_forest(forest)
         if boost is not None:
             eng.set_boost(boost)
+        if svm is not None:
+            eng.set_svm(svm)
         _ENGINES[key] = (eng, constraints, classifier, ml_scaler)  # keep referents alive
         return eng
     return eng[0]
